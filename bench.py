@@ -13,11 +13,20 @@ Launch: under torchrun (RANK / LOCAL_RANK / WORLD_SIZE in the environment) every
 with N > 1 starts the N rank processes itself (fresh children, started before the parent touches the GPU) and forwards rank 0's line.
 A run that was asked for N GPUs never prints a line for fewer.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run does only what that
+headline needs: set up, warm up, time the --steps training steps, write --dump-outputs if given, print the line; its `roofline`
+object holds the whole-step figures that follow from the step time alone (algorithmic bytes / FLOPs of SURVEY.md section 8d).
+--full adds the secondary measurements, each a run or an instrumentation of its own:
   roofline     - the dominant kernel (3^3 implicit-GEMM conv on bf16 MFMA): algorithmic FLOPs of its launches in the
-                 timed region / their summed HIP-event durations, against the 2.5 PFLOP/s dense bf16 MFMA peak;
-                 plus the whole-step HBM fraction (algorithmic bytes of SURVEY.md section 8d / step time / 8 TB/s).
-  cpu_baseline - the oracle (plain torch CPU fp32, kind "port") timed on this host's cores on a bounded sample.
+                 timed region / their summed HIP-event durations, against the 2.5 PFLOP/s dense bf16 MFMA peak
+                 (per-launch HIP events on every 5th timed step; --no-kernel-events drops them, --all-kernel-events times every launch);
+  sample       - an n-step reverse-diffusion sample of one cube per rank (--sample-steps, default 1000 under --full);
+  cpu_baseline - the oracle (plain torch CPU fp32, kind "port") timed on this host's cores on a bounded sample (--no-cpu-baseline drops it).
+--graph (also times the step as one hipGraph replay) and --sample-only stay explicit options, as do --sample-steps / --all-kernel-events,
+which take effect without --full too.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller as float32 .npy files (see dump_outputs);
+the inputs (weights, batch, noise seeds) depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -65,6 +74,24 @@ def build_model(D, chs, precision, device, seed=42):
     return LightVDM(score_model=net, draw_figure=None, gamma_max=13.3, learning_rate=3.0e-4).to(device)
 
 
+DUMP_SAMPLE = 1 << 22      # --dump-outputs keeps at most this many values per array (16 MB of float32; the dump stays under 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: tensor} -> path/<name>.npy, float32 (float64 kept as is), flattened.  A tensor of more than DUMP_SAMPLE
+    values is written as its values at DUMP_SAMPLE sorted positions drawn by a fixed seed from its size alone: the same positions in
+    every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(20241016))[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        t = t.cpu()
+        np.save(os.path.join(path, f"{name}.npy"), t.numpy() if t.dtype == torch.float64 else t.float().numpy())
+
+
 def make_batch(D, B, rank, device):
     from vdm4cdm_amd.data import SyntheticAstroDataModule
     dm = SyntheticAstroDataModule(cropsize=D, batch_size=B, seed=1000 + rank)
@@ -102,7 +129,8 @@ def cpu_baseline(chs):
     """the oracle (this repo's fp32 torch-CPU restatement of the path; kind "port") on the host cores -
     C2 (64^3, batch 2) and 128^3 batch 1, UNet fwd+bwd, 1 warm-up + 3 timed iterations each, median.  `value` is the 128^3 number
     (the metric's cube size); the C2 number rides along."""
-    cores = min(os.cpu_count() or 1, 64)          # oneDNN does not scale these convs past a few dozen threads
+    # oneDNN does not scale these convs past a few dozen threads; an OMP_NUM_THREADS of the environment (a CPU share) is the limit
+    cores = min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 64)
     torch.set_num_threads(cores)
     t64, w64 = _oracle_fwd_bwd_seconds(chs, 64, 2, 3)
     t128, w128 = _oracle_fwd_bwd_seconds(chs, 128, 1, 3)
@@ -115,11 +143,12 @@ def cpu_baseline(chs):
 
 def sample_leg(args, vdm, batch, D, device, rank, world):
     """One `--sample-steps`-step chain of one 128^3 cube PER RANK (hipGraph-captured denoise step, in-kernel Philox noise).  Returns the
-    "sample" object on rank 0 (None elsewhere; every rank gets {"error": ...} if any chain failed).  N = 1: exactly the round-3 leg
-    (seed 1234, z_1 from the global generator); N > 1: chain id = rank, seed = entry.chain_seed(rank) for the chain AND its z_1."""
+    "sample" object on rank 0 (None elsewhere; every rank gets {"error": ...} if any chain failed) and this rank's sampled cube (None if
+    its chain failed).  N = 1: exactly the round-3 leg (seed 1234, z_1 from the global generator); N > 1: chain id = rank,
+    seed = entry.chain_seed(rank) for the chain AND its z_1."""
     import torch.distributed as dist
     from vdm4cdm_amd.entry import chain_seed
-    res, err = {}, None
+    res, err, z = {}, None, None
     try:
         vdm.eval()
         s = batch["conditioning"][:1]
@@ -147,12 +176,12 @@ def sample_leg(args, vdm, batch, D, device, rank, world):
         per = [None] * world
         dist.all_gather_object(per, dict(res, error=err) if err else res)
     if rank != 0:
-        return {"error": "a chain failed"} if any("error" in p for p in per) else None
+        return ({"error": "a chain failed"} if any("error" in p for p in per) else None), z
     out = {"steps": args.sample_steps, "cube": D, "batch": 1, "chains": world}
     bad = [(r, p["error"]) for r, p in enumerate(per) if "error" in p]
     if bad:
         out["error"] = f"(rank, error): {bad}"
-        return out
+        return out, z
     smax = max(p["seconds"] for p in per)
     out.update(seconds=smax, steps_per_s=args.sample_steps / smax, finite=all(p["finite"] for p in per), std=per[0]["std"], mean=per[0]["mean"],
                seconds_max=smax, seconds_per_rank=[p["seconds"] for p in per], seeds=[p["seed"] for p in per],
@@ -164,7 +193,7 @@ def sample_leg(args, vdm, batch, D, device, rank, world):
             "value": 2.50, "unit": "denoise steps/s", "steps": 250, "cube": 256, "chs": [16, 32, 64, 128],
             "hardware": "one NVIDIA GPU of the 80 GB class (model not stated)",
             "source": "/root/reference ICML_figures.ipynb cell 103 (tqdm rate), configs.yaml:127-143, generate_3D.py:61"}
-    return out
+    return out, z
 
 
 def self_spawn(n, argv):
@@ -199,8 +228,16 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP events (pure wall-clock run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: per-launch kernel events with the roofline of the dominant kernel, the "
+                         "--sample-steps reverse-diffusion sample (default 1000 steps) and the CPU baseline.  Without it a run only sets up, "
+                         "warms up, times the --steps training steps (no per-launch events) and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one handed its caller to DIR/<name>.npy (float32): the loss, and the "
+                         "parameters and clipped gradient the step left in the flat vector (a fixed, seeded sample of 4 Mi values each); "
+                         "with --sample-only the sampled cube instead")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full without per-launch HIP events (pure wall-clock run)")
     ap.add_argument("--all-kernel-events", action="store_true",
                     help="HIP events around EVERY kernel launch (full per-kernel table; ~600 event pairs per step cost ~6 %% of the step)."
                          " Default: only the 3^3 conv fwd/dgrad launches, the candidates for the dominant kernel (~50 per step)")
@@ -211,10 +248,14 @@ def main():
     ap.add_argument("--sample-only", action="store_true",
                     help="skip the training steps: only the --sample-steps reverse-diffusion sample is timed (e.g. --config c256 "
                          "--sample-steps 250, the configuration of the reference's one published rate)")
-    ap.add_argument("--sample-steps", type=int, default=1000,
+    ap.add_argument("--sample-steps", type=int, default=None,
                     help="after the training steps, rank 0 also times an n-step reverse-diffusion sample of one cube (second half of the "
-                         "BASELINE metric: 1000-step sample wall-clock; reported under \"sample\", never part of \"value\"); 0 = skip")
+                         "BASELINE metric: 1000-step sample wall-clock; reported under \"sample\", never part of \"value\"); 0 = skip.  "
+                         "Default: 1000 with --full or --sample-only, else 0")
     args = ap.parse_args()
+    if args.sample_steps is None:
+        args.sample_steps = 1000 if (args.full or args.sample_only) else 0
+    kernel_events = (args.full or args.all_kernel_events) and not args.no_kernel_events
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # plain `python bench.py --gpus N`: become the launcher
         sys.exit(self_spawn(args.gpus, sys.argv[1:]))
 
@@ -262,7 +303,7 @@ def main():
             step()
         for _ in range(args.warmup):
             step()
-        if not args.no_kernel_events:
+        if kernel_events:
             prof = hip_ops.PROFILER = hip_ops.KernelProfiler(None if args.all_kernel_events else {"conv3", "wgrad"})
         if world > 1:
             dist.barrier()
@@ -284,6 +325,8 @@ def main():
             per_step.append(time.perf_counter())
             print("per-step ms:", " ".join(f"{1e3 * (b - a):.2f}" for a, b in zip(per_step, per_step[1:])), file=sys.stderr, flush=True)
         hip_ops.PROFILER = None
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"loss": loss, "params": net.flat, "grad": net.flat.grad})
         loss = float(loss.detach())          # (drop the autograd graph of the last eager step: a live AccumulateGrad node bound to the
                                              # default stream would be run inside the stream capture of the graphed step below)
         el = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -302,7 +345,9 @@ def main():
     # id as entry.generate_3d does; the ranks start together (barrier) and rank 0 reports the slowest chain and the aggregate rate.
     sample_res = None
     if args.sample_steps:
-        sample_res = sample_leg(args, vdm, batch, D, device, rank, world)
+        sample_res, z = sample_leg(args, vdm, batch, D, device, rank, world)
+        if args.sample_only and args.dump_outputs and rank == 0 and z is not None:
+            dump_outputs(args.dump_outputs, {"sample": z})
 
     if rank == 0:
         scale = 1.0 if chs == [32, 64, 128, 256] else None
@@ -411,7 +456,7 @@ def main():
                 hip_ops.SEED_STEP = None
         if sample_res is not None:
             out["sample"] = sample_res
-        if not args.no_cpu_baseline and world == 1 and not args.sample_only:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.sample_only:
             try:
                 out["cpu_baseline"] = cpu_baseline(chs)
             except Exception as e:                          # never lose the GPU line over the host-side baseline

@@ -227,7 +227,8 @@ def test_bench_self_spawn_two_ranks_share_one_gpu():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(VDM4CDM_SHARE_GPU="1", VDM4CDM_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--sample-steps", "12"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
+           "--sample-steps", "12"]
     r = subprocess.run(cmd + ["--gpus", "2"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -250,6 +251,27 @@ def test_bench_self_spawn_two_ranks_share_one_gpu():
                        text=True, timeout=900)
     assert r.returncode != 0 and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "refusing" in r.stderr
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) prints the headline line only - no per-kernel table, sample or CPU baseline - and
+    --dump-outputs writes what the last timed step handed its caller: its loss (the line's), the parameters and the gradient."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "tiny", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "voxels/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] == pytest.approx(2 * 32 ** 3 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert not {"kernels", "sample", "cpu_baseline", "graph_step"} & set(d) and "kernel" not in d["roofline"]
+    files = {f.name: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert set(files) == {"loss.npy", "params.npy", "grad.npy"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert files["loss.npy"].shape == (1,) and float(files["loss.npy"][0]) == pytest.approx(d["loss"], rel=1e-6)
+    assert files["params.npy"].shape == files["grad.npy"].shape and np.abs(files["grad.npy"]).max() > 0
 
 
 def _ss_cases():

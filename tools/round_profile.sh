@@ -41,9 +41,9 @@ if [ -f vdm4cdm_amd/libvdm4cdm_hip_timeline.so ]; then
     VDM4CDM_WGRAD_WGS=256 VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_32_32
     VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_64_32 ) 2>&1 | grep -v amdgpu.ids > "$out/${tag}_wgrad_phases.txt"
 fi
-python bench.py --config c2 --steps 40 --warmup 5 --no-cpu-baseline --sample-steps 0 > "$out/${tag}_bench_c2.json" 2>/dev/null
-# the default bench line LAST: its roofline object reads the counter tables of THIS profile (static files under profiles/)
+python bench.py --config c2 --steps 40 --warmup 5 --full --no-cpu-baseline --sample-steps 0 > "$out/${tag}_bench_c2.json" 2>/dev/null
+# the full bench line LAST: its roofline object reads the counter tables of THIS profile (static files under profiles/)
 cp "$out/${tag}_pmc_bench_traffic.json" "$out/${tag}_pmc_mfma_util.json" profiles/ 2>/dev/null || true
-python bench.py > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err"
+python bench.py --full > "$out/${tag}_bench_c3.json" 2> "$out/${tag}_bench_c3.err"
 echo "bench done"
 echo done
