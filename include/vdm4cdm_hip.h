@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 11
+#define VDM_ABI_VERSION 12
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -360,6 +360,12 @@ int vdm_ancestral_step(float* z, const float* eps_hat, const float* noise, const
  * one batch-doubled UNet forward: given v_conditionings / masked v_conditionings). */
 int vdm_ancestral_step_cfg(float* z, const float* eps_cond, const float* eps_uncond, float w_cfg, const float* noise,
                            const float* coef, const int32_t* step_ptr, uint64_t seed, int64_t n, void* stream);
+/* Row-keyed form for batched chains: z is [rows][per_row]; row r's noise is the Philox normal of (seeds[r], *step_ptr + 1, float4 group
+ * index within the row), so a chain draws the same noise wherever it sits in a batch (rows == 1: the stream of vdm_ancestral_step with
+ * seed = seeds[0], bit for bit).  eps_uncond == NULL: plain update; otherwise the w_cfg blend of vdm_ancestral_step_cfg.  seeds is a
+ * DEVICE array of `rows` values; per_row must be a positive multiple of 4 and the three fields 16-byte aligned. */
+int vdm_ancestral_step_rows(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const float* coef,
+                            const int32_t* step_ptr, const uint64_t* seeds, int rows, int64_t per_row, void* stream);
 /* standard-normal fill from Philox(seed, stream_id) (z_1 of the sampler; eps in training). */
 int vdm_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, const int32_t* seed_step, void* stream);
 /* *step_ptr += 1 (device-side step counter for the captured sampler graph). */

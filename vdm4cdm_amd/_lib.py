@@ -66,7 +66,7 @@ class AugmentSample(C.Structure):
 PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
-ABI_VERSION = 11                      # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 12                      # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -120,6 +120,7 @@ SIGNATURES = {
     "vdm_loss_terms_rng": (_i, [_p, _p, _u64, _u64, _p, _p, _u64, _u64, _p, _f, _p, _i, _i64, _p, _p, _p, _p]),
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),
+    "vdm_ancestral_step_rows": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i64, _p]),
     "vdm_randn": (_i, [_p, _i64, _u64, _u64, _p, _p]),
     "vdm_step_inc": (_i, [_p, _p]),
     "vdm_sumsq": (_i, [_p, _i64, _p, _p, _p]),

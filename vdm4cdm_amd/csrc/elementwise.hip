@@ -719,8 +719,25 @@ __global__ void __launch_bounds__(256) loss_terms_rng_kernel(const float* __rest
     }
 }
 
-// eu != NULL: classifier-free guidance - the noise estimate is (1 + w) * eh - w * eu (conditional / v-masked UNet outputs, the two
-// halves of one batch-doubled forward), blended here so that the guided estimate never exists in memory.
+// A product rounded on its own: the empty asm hides it from -ffp-contract=fast, which would otherwise fuse it into the add that consumes
+// it wherever the vectoriser happens not to pack the two products (no instruction is emitted).
+__device__ __forceinline__ float uncontracted_mul(float a, float b) {
+    float p = a * b;
+    asm("" : "+v"(p));
+    return p;
+}
+
+// One element of the ancestral update z <- ratio * (z - cs * e) + scale * noise, shared by ancestral_kernel and ancestral_rows_kernel.
+// The rounding is spelled out - fma(-cs, e, z), then the two products rounded and added - which is what ancestral_kernel has always
+// compiled to, so the row-keyed kernel gives the same bits whatever the compiler packs.  cfg: classifier-free guidance - the noise
+// estimate is (1 + w) * eh - w * eu (conditional / v-masked UNet outputs, the two halves of one batch-doubled forward), blended here so
+// that the guided estimate never exists in memory.
+__device__ __forceinline__ float ancestral_update(float z, float eh, float eu, bool cfg, float w, float ratio, float cs, float scale,
+                                                  float nz) {
+    const float e = cfg ? uncontracted_mul(1.f + w, eh) - uncontracted_mul(w, eu) : eh;
+    return uncontracted_mul(ratio, fmaf(-cs, e, z)) + uncontracted_mul(scale, nz);
+}
+
 __global__ void __launch_bounds__(256) ancestral_kernel(float* __restrict__ z, const float* __restrict__ eh,
                                                        const float* __restrict__ eu, float w,
                                                        const float* __restrict__ noise, const float* __restrict__ coef,
@@ -738,11 +755,36 @@ __global__ void __launch_bounds__(256) ancestral_kernel(float* __restrict__ z, c
         }
         for (int j = 0; j < 4; ++j) {
             const int64_t k = i * 4 + j;
-            if (k < n) {
-                const float e = eu ? (1.f + w) * eh[k] - w * eu[k] : eh[k];
-                z[k] = ratio * (z[k] - cs * e) + scale * nz[j];
-            }
+            if (k < n) z[k] = ancestral_update(z[k], eh[k], eu ? eu[k] : 0.f, eu != nullptr, w, ratio, cs, scale, nz[j]);
         }
+    }
+}
+
+// Row-keyed form: row r (blockIdx.y) of z [rows][per] draws its noise from (seeds[r], step + 1, float4 group index within the row), so a
+// chain's noise does not depend on the batch it is sampled in (rows == 1: the stream of ancestral_kernel with seed = seeds[0]).
+// per % 4 == 0 and 16-byte aligned rows (checked by the entry point).
+__global__ void __launch_bounds__(256) ancestral_rows_kernel(float* __restrict__ z, const float* __restrict__ eh,
+                                                            const float* __restrict__ eu, float w, const float* __restrict__ coef,
+                                                            const int32_t* __restrict__ step_ptr, const uint64_t* __restrict__ seeds,
+                                                            int64_t per) {
+    const int step = *step_ptr;
+    const float ratio = coef[step * 4 + 0], cs = coef[step * 4 + 1], scale = coef[step * 4 + 2];
+    const uint64_t seed = seeds[blockIdx.y];
+    const size_t base = (size_t)blockIdx.y * per;
+    const int64_t n4 = per >> 2;
+    float4* z4 = reinterpret_cast<float4*>(z + base);
+    const float4* h4 = reinterpret_cast<const float4*>(eh + base);
+    const float4* u4 = eu ? reinterpret_cast<const float4*>(eu + base) : nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 r = randn4(seed, (uint64_t)(step + 1), (uint64_t)i);
+        const float4 hv = h4[i];
+        const float4 uv = u4 ? u4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 zv = z4[i];
+        zv.x = ancestral_update(zv.x, hv.x, uv.x, u4 != nullptr, w, ratio, cs, scale, r.x);
+        zv.y = ancestral_update(zv.y, hv.y, uv.y, u4 != nullptr, w, ratio, cs, scale, r.y);
+        zv.z = ancestral_update(zv.z, hv.z, uv.z, u4 != nullptr, w, ratio, cs, scale, r.z);
+        zv.w = ancestral_update(zv.w, hv.w, uv.w, u4 != nullptr, w, ratio, cs, scale, r.w);
+        z4[i] = zv;
     }
 }
 
@@ -1123,6 +1165,23 @@ extern "C" int vdm_ancestral_step_cfg(float* z, const float* eps_cond, const flo
     hipLaunchKernelGGL(ancestral_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, z, eps_cond, eps_uncond, w_cfg,
                        noise, coef, step_ptr, seed, n);
     VDM_LAUNCH_CHECK("ancestral_kernel(cfg)");
+    return VDM_OK;
+}
+
+extern "C" int vdm_ancestral_step_rows(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const float* coef,
+                                       const int32_t* step_ptr, const uint64_t* seeds, int rows, int64_t per_row, void* stream) {
+    VDM_REQUIRE(z && eps_hat && coef && step_ptr, "ancestral_step_rows: null z / eps_hat / coef / step_ptr");
+    VDM_REQUIRE(seeds, "ancestral_step_rows: seeds is NULL (one device seed per row)");
+    VDM_REQUIRE(rows > 0 && rows <= 65535, "ancestral_step_rows: rows = %d (1 .. 65535)", rows);
+    VDM_REQUIRE(per_row > 0 && per_row % 4 == 0, "ancestral_step_rows: per_row = %lld (a positive multiple of 4)", (long long)per_row);
+    VDM_REQUIRE(((uintptr_t)z | (uintptr_t)eps_hat | (uintptr_t)eps_uncond) % 16 == 0,
+                "ancestral_step_rows: z / eps_hat / eps_uncond must be 16-byte aligned");
+    // ~2048 workgroups in all, as the one-seed kernel: the rows share the grid, each grid-strides over its own row
+    int64_t bx = (per_row / 4 + 255) / 256, cap = (2048 + rows - 1) / rows;
+    if (bx > cap) bx = cap;
+    hipLaunchKernelGGL(ancestral_rows_kernel, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, z, eps_hat, eps_uncond,
+                       w_cfg, coef, step_ptr, seeds, per_row);
+    VDM_LAUNCH_CHECK("ancestral_rows_kernel");
     return VDM_OK;
 }
 

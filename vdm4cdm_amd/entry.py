@@ -9,7 +9,8 @@
   ``trainSFM_c_uc_from_field_name.py <field_in> <field_out>`` (mid-level attention on) -> ``train_sfm_c_uc_2d(argv)``.
 * ``generate_3D.py <model_name> <save_path> <runtype>`` -> ``generate_3d(argv)`` (/root/reference/generate_3D.py).
 Environment knobs (build-side, all optional): VDM4CDM_MAX_STEPS, VDM4CDM_PRECISION (bf16|fp32), VDM4CDM_SAMPLING_STEPS,
-VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing config).
+VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing config), VDM4CDM_SAMPLE_BATCH (chains per sampler
+call and rank in generate_3D*; default 1).
 Multi-GPU: launch the same script under ``python -m torch.distributed.run --nproc-per-node N`` (one rank per GPU, RCCL).
 """
 import argparse
@@ -245,18 +246,33 @@ def _sampling_setup(model_name, configs_path, set_name):
     return rank, world, device, config, model, dm
 
 
-def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, world, n_steps):
-    """The `rep` independent chains of one conditioning cube that fall to this rank: [(repetition index, sample)]."""
+def _sample_batch():
+    """VDM4CDM_SAMPLE_BATCH: the number of chains one sampler call (one hipGraph replay per step) carries, per rank; default 1.  Read
+    before any model or GPU work, so that a bad value fails at once."""
+    raw = os.environ.get("VDM4CDM_SAMPLE_BATCH", "1")
+    if not raw.strip().isdigit() or int(raw) < 1:
+        raise SystemExit(f"VDM4CDM_SAMPLE_BATCH={raw!r}: must be a positive integer (chains per sampler call and rank)")
+    return int(raw)
+
+
+def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, world, n_steps, per_call=1):
+    """The `rep` independent chains of one conditioning cube that fall to this rank: [(repetition index, sample)].  The rank's chains
+    are sampled `per_call` at a time; every chain is keyed by its own seed (VDM.sample(seeds=)), so its cube does not depend on the
+    batch it was sampled in."""
     s_conditioning = batch["conditioning"].to(device)
     v_conditionings = [d.to(device) for d in batch["conditioning_values"]] if config.get("conditioning_values", 6) else []
+    mine = [i for i in range(rep) if (first_chain + i) % world == rank]    # global chain id first_chain + i: dealt round-robin to ranks
     out = []
-    for i in range(rep):
-        chain = first_chain + i                              # global chain id: the unit that is dealt to the ranks
-        if chain % world != rank:
-            continue
-        gen = model.draw_samples(batch_size=1, n_sampling_steps=n_steps, seed=chain_seed(chain), s_conditioning=s_conditioning,
-                                 v_conditionings=v_conditionings, verbose=(rank == 0))
-        out.append((i, gen.detach().cpu().numpy()))
+    for k in range(0, len(mine), per_call):
+        ids = mine[k:k + per_call]
+        if per_call == 1:
+            gen = model.draw_samples(batch_size=1, n_sampling_steps=n_steps, seed=chain_seed(first_chain + ids[0]),
+                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0))
+        else:
+            gen = model.draw_samples(batch_size=len(ids), n_sampling_steps=n_steps, seeds=[chain_seed(first_chain + i) for i in ids],
+                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0))
+        gen = gen.detach().cpu().numpy()
+        out.extend((i, gen[j:j + 1]) for j, i in enumerate(ids))
     return out
 
 
@@ -301,6 +317,7 @@ def generate_3d(argv=None, configs_path=None):
     if "SFM" in args.model_name:
         raise NotImplementedError("This model is not implemented yet")
     assert args.runtype in ["CV_12_12", "CV_1_128"]
+    per_call = _sample_batch()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "CV")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -310,7 +327,7 @@ def generate_3d(argv=None, configs_path=None):
     for i_batch, batch in enumerate(dm.test_dataloader()):
         if sel is not None and i_batch != sel:
             continue
-        parts = _sample_repetitions(model, config, batch, device, rep, count * rep, rank, world, n_steps)
+        parts = _sample_repetitions(model, config, batch, device, rep, count * rep, rank, world, n_steps, per_call)
         _save_or_shard(args.save_path, f"gen_{count}", parts, rank, world)
         count += 1
         if count == n_cubes:
@@ -336,6 +353,7 @@ def generate_3d_1p(argv=None, configs_path=None):
         raise NotImplementedError("This model is not implemented yet")
     if args.runtype not in ["1P_24", "1P_128"]:
         raise NotImplementedError("This runtype is not implemented yet")
+    per_call = _sample_batch()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "1P")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -347,7 +365,7 @@ def generate_3d_1p(argv=None, configs_path=None):
         k = ONE_P_GENS.index(i_batch)
         if rank == 0:
             print(ONE_P_NAMES[k], "params", batch["conditioning_values"], flush=True)
-        parts = _sample_repetitions(model, config, batch, device, rep, k * rep, rank, world, n_steps)
+        parts = _sample_repetitions(model, config, batch, device, rep, k * rep, rank, world, n_steps, per_call)
         stems.append(f"{ONE_P_NAMES[k]}_{rep}")
         _save_or_shard(args.save_path, stems[-1], parts, rank, world)
     _merge_shards(args.save_path, stems, rep, rank, world)

@@ -792,6 +792,19 @@ def ancestral_step(z, eps_hat, noise, coef, step_ptr, seed, eps_uncond=None, w_c
                                        z.numel(), _s()), "vdm_ancestral_step_cfg")
 
 
+def ancestral_step_rows(z, eps_hat, coef, step_ptr, seeds_dev, eps_uncond=None, w_cfg=0.0):
+    """K9, row-keyed: row r of z ([rows, ...]) draws its noise from seeds_dev[r] (a device int64 tensor of `rows` seeds), so a chain's
+    noise is the same in any batch; rows == 1 gives ancestral_step(seed=seeds_dev[0]) bit for bit.  eps_uncond: the w_cfg blend."""
+    L = _lib.lib()
+    _contig(z, eps_hat, coef, eps_uncond, seeds_dev)
+    rows = z.shape[0]
+    assert eps_hat.shape == z.shape and z.dtype == eps_hat.dtype == torch.float32
+    assert eps_uncond is None or (eps_uncond.shape == z.shape and eps_uncond.dtype == torch.float32)
+    assert seeds_dev.dtype == torch.int64 and seeds_dev.numel() == rows and seeds_dev.device == z.device
+    check(L.vdm_ancestral_step_rows(_p(z), _p(eps_hat), _p(eps_uncond), float(w_cfg), _p(coef), _p(step_ptr), _p(seeds_dev), rows,
+                                    z.numel() // rows, _s()), "vdm_ancestral_step_rows")
+
+
 def randn(out, seed, stream_id=0):
     L = _lib.lib()
     _contig(out)

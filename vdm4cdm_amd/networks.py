@@ -353,6 +353,8 @@ class CUNet(nn.Module):
             head = self.flat[:self.head_end]
             conds = self.cond_vectors(t, v_conditionings, head)
             table = self.cond_table(conds, B, head)
+            if s_conditioning is not None and s_conditioning.shape[0] != B:     # one conditioning field for the whole batch
+                s_conditioning = s_conditioning.expand(B, *s_conditioning.shape[1:])
             return self._forward_torch(x, s_conditioning, table)
         if self.dim != 3 or self.in_channels != 1 or self.s_conditioning_channels > 1:
             raise NotImplementedError("the HIP backend covers the 3D, single-field configurations of the reference "

@@ -573,9 +573,10 @@ def hip_unet_apply(net, x, s_conditioning, table=None, t=None, v_conditionings=N
     s = None
     if net.s_conditioning_channels:
         assert s_conditioning is not None, "s_conditioning_channels=1 needs s_conditioning"
-        s = s_conditioning.to(torch.float32).reshape(B, *x.shape[2:]).contiguous()
-        if s.shape[0] != B:
-            s = s.expand(B, *s.shape[1:]).contiguous()
+        s = s_conditioning.to(torch.float32)
+        if s.shape[0] != B:                                # one conditioning cube for the whole batch
+            s = s.expand(B, *s.shape[1:])
+        s = s.reshape(B, *x.shape[2:]).contiguous()
     vs = []
     if table is None:
         if t is not None:

@@ -295,18 +295,29 @@ class VDM(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch_size, n_sampling_steps, device, z=None, return_all=False, verbose=False,
-               noises=None, seed=None, use_graph=True, **kwargs):
+               noises=None, seed=None, use_graph=True, seeds=None, **kwargs):
         """Ancestral sampling (notebook frame vdm_model.py:429-442).  `noises` (optional list of n tensors) and
-        `seed` make a chain reproducible; on the HIP backend the step is a replayed hipGraph."""
+        `seed` make a chain reproducible; on the HIP backend the step is a replayed hipGraph.
+        `seeds` (one int per row): every row is a chain of its own, keyed by its seed wherever it sits in the batch - row r draws z_1
+        and its step noise exactly as a batch-1 chain with seed=seeds[r] does (a supplied z: the seeds key the step noise only).
+        `seed` with batch_size > 1 keeps its meaning of one stream for the whole batch."""
+        if seeds is not None:
+            seeds = [int(s) for s in seeds]
+            if len(seeds) != batch_size:
+                raise ValueError(f"sample: {len(seeds)} seeds for batch_size={batch_size} (one seed per chain)")
+            if seed is not None or noises is not None:
+                raise ValueError("sample: seeds= cannot be combined with seed= or noises=")
         shape = (batch_size, *self.score_model.shape)
-        if z is None:
+        if z is None and seeds is not None:
+            z = torch.cat([torch.randn((1, *self.score_model.shape), generator=torch.Generator().manual_seed(s)) for s in seeds]).to(device)
+        elif z is None:
             z = torch.randn(shape, device=device) if seed is None else \
                 torch.randn(shape, generator=torch.Generator().manual_seed(int(seed))).to(device)
         else:
             z = z.clone()                                    # the HIP path updates z in place: never the caller's tensor
         z = z.to(device=device, dtype=torch.float32).contiguous()
         if self._hip(z):                                     # (return_all: the same captured step, z copied out after every replay)
-            return self._sample_hip(z, n_sampling_steps, noises, seed, verbose, use_graph, kwargs, return_all)
+            return self._sample_hip(z, n_sampling_steps, noises, seed, verbose, use_graph, kwargs, return_all, seeds)
         steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1, device=device)
         zs = []
         rng = range(n_sampling_steps)
@@ -316,44 +327,60 @@ class VDM(nn.Module):
                 rng = trange(n_sampling_steps, desc="sampling")
             except ImportError:
                 pass
-        gen = None
+        gen = gens = None
         if noises is None and seed is not None:              # a seeded chain is reproducible on this path too (per-step noise from
             gen = torch.Generator().manual_seed(int(seed) + 1)   # the chain's own generator, not the global RNG)
+        if seeds is not None:                                # per-chain seeds: every row its own generator, a (1, ...) draw per step
+            gens = [torch.Generator().manual_seed(s + 1) for s in seeds]
         for i in rng:
-            if noises is None and gen is None:
+            if noises is None and gen is None and gens is None:
                 z = self.sample_zs_given_zt(zt=z, t=steps[i], s=steps[i + 1], **kwargs)
             else:
                 w_z, w_x, x0, scale = self.sample_zs_given_zt(zt=z, t=steps[i], s=steps[i + 1], return_ddnm=True, **kwargs)
-                eps = noises[i].to(z) if noises is not None else torch.randn(z.shape, generator=gen).to(z)
+                if noises is not None:
+                    eps = noises[i].to(z)
+                elif gens is not None:
+                    eps = torch.cat([torch.randn((1, *z.shape[1:]), generator=g) for g in gens]).to(z)
+                else:
+                    eps = torch.randn(z.shape, generator=gen).to(z)
                 z = w_z * z + w_x * x0 + scale * eps
             if return_all:
                 zs.append(z)
         return torch.stack(zs, dim=0) if return_all else z
 
-    def _sample_hip(self, z, n, noises, seed, verbose, use_graph, kwargs, return_all=False):
+    def _sample_hip(self, z, n, noises, seed, verbose, use_graph, kwargs, return_all=False, seeds=None):
         coef = self.step_table(n).to(device=z.device, dtype=torch.float32).contiguous()
         cfg = self.w_cfg is not None and not self.training
         if cfg:
             assert "v_conditionings" in kwargs, "Need v_conditionings to mask out"
         return hip_graph_sampler(self.score_model, z, coef, noises, seed, verbose, use_graph, kwargs.get("s_conditioning"),
                                  list(kwargs.get("v_conditionings") or []), w_cfg=float(self.w_cfg) if cfg else None,
-                                 mask_fn=self.cfg_mask, return_all=return_all)
+                                 mask_fn=self.cfg_mask, return_all=return_all, seeds=seeds)
 
 
 def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None,
-                      return_all=False):
+                      return_all=False, seeds=None):
     """The multi-step sampling loop on the HIP backend, shared by the VDM ancestral sampler and the SFM Euler integrator: per step
     [conditioning-table row gather, UNet forward, fused update z <- ratio * (z - cs * net_out) + scale * noise, step counter + 1],
     captured once in a hipGraph and replayed; coef[n][4] = {ratio, cs, scale, network time} is read on the device at the row of the
     device-side step counter.  z is updated in place and returned; return_all: the stack [n, B, ...] of z after every step instead
-    (frame vdm_model.py:429-442: ``return_all``), copied out between the replays of the same graph."""
+    (frame vdm_model.py:429-442: ``return_all``), copied out between the replays of the same graph.
+    seeds (one int per row of z): the update draws row r's noise from seeds[r] (vdm_ancestral_step_rows) instead of one stream for the
+    whole batch from `seed`; the seed table is uploaded here, before the capture."""
     from . import hip_ops as ops
     from .unet_hip import hip_unet_apply
     dev = z.device
     n = coef.shape[0]
     step = torch.zeros(1, dtype=torch.int32, device=dev)
     B = z.shape[0]
-    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+    seeds_dev = None
+    if seeds is not None:
+        assert len(seeds) == B and noises is None
+        seeds_dev = torch.tensor([int(s) for s in seeds], dtype=torch.int64, device=dev)
+    elif seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    else:
+        seed = int(seed)
     noise_buf = torch.empty_like(z) if noises is not None else None
 
     # The conditioning of every step is known up front: ONE K6 launch embeds all n time values (one table row per step), one more
@@ -371,9 +398,9 @@ def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_
         R = 2 * B if cfg else B                            # rows the UNet sees
         if vs:
             table_v = ops.CondTable(net.cond_specs(None, vs, fl, which="v"), R, W).forward(save=False)
-    if cfg and s_cond is not None:
+    if s_cond is not None:                                 # one conditioning cube serves every row of the batch
         s_cond = s_cond.to(dev).expand(B, *s_cond.shape[1:])
-        s_cond = torch.cat([s_cond, s_cond], dim=0).contiguous()
+        s_cond = (torch.cat([s_cond, s_cond], dim=0) if cfg else s_cond).contiguous()
     table = torch.zeros(R, W, device=dev)
     zz = torch.empty(R, *z.shape[1:], device=dev) if cfg else z
 
@@ -384,7 +411,10 @@ def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_
             zz[:B].copy_(z)
             zz[B:].copy_(z)
         eps_hat = hip_unet_apply(net, zz, s_cond, table=table).contiguous()
-        if cfg:                                            # blend inside K9: the guided estimate is never materialised
+        if seeds_dev is not None:                          # row-keyed noise: chain r's stream is seeds[r]'s, in any batch
+            ops.ancestral_step_rows(z, eps_hat[:B], coef, step, seeds_dev, eps_uncond=eps_hat[B:] if cfg else None,
+                                    w_cfg=w_cfg if cfg else 0.0)
+        elif cfg:                                          # blend inside K9: the guided estimate is never materialised
             ops.ancestral_step(z, eps_hat[:B], noise_buf, coef, step, seed, eps_uncond=eps_hat[B:], w_cfg=w_cfg)
         else:
             ops.ancestral_step(z, eps_hat, noise_buf, coef, step, seed)
