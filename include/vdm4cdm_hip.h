@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 12
+#define VDM_ABI_VERSION 13
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -263,6 +263,13 @@ int vdm_cond_table_bwd(const vdm_cond_mlp* mlps, int n, int rows, int width, con
                        const float* saved, float* scratch, float* dbias, void* stream);
 int vdm_cond_table_step(const float* table_t, const float* table_v, const int32_t* step_ptr, int rows, int width, float* out,
                         void* stream);
+/* K6i (ABI v13): input gradients of the conditioning MLPs, enqueued after vdm_cond_table_bwd with the same mlps / rows / width, saved and
+ * scratch (it reads the dh1 rows the backward left there): d input = W1^T dh1 per row.  host_dinputs: a HOST array of n DEVICE pointers
+ * (4-byte aligned; NULL = not wanted): a vector conditioning receives [rows][in_dim], the sinusoidal t embedding the chain rule through
+ * [sin(1000 t f_i), cos(1000 t f_i)] folded into one dL/dt per row ([rows]).  Guidance / inverse problems / learned noise schedules
+ * [NB vdm_model.py:320-324: t = (gamma_t - gamma_min) / (gamma_max - gamma_min)]. */
+int vdm_cond_input_grad(const vdm_cond_mlp* mlps, int n, int rows, int width, const float* saved, const float* scratch,
+                        float* const* host_dinputs, void* stream);
 
 /* ---- K7/K8: VDM forward diffusion + ELBO pieces [R7; D9/D10] -----------------------------------
  * z_t = alpha[n] x + sigma[n] eps  (fp32, contiguous per sample of `per` elements). */
@@ -288,6 +295,20 @@ int vdm_diffuse_pack(const float* x, const float* s_cond, const float* eps, uint
 int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps, const float* eps_hat, const float* eps0,
                        uint64_t seed_eps0, uint64_t stream_eps0, const int32_t* seed_step, float sigma0_over_alpha0, const float* coef, int n,
                        int64_t per, float* sums, float* d_eps_hat, float* workspace, void* stream);
+
+/* ---- input gradients of the network and the learned schedule (ABI v13) [noise_schedule="learned_linear",
+ * REF train3D_c_c_from_field_name.py:124-129] -------------------------------------------------------------------------------------
+ * K1t conv_in_dgrad: dz / ds = the gradient w.r.t. conv_in's two input channels (z_t, s_conditioning) from dh = d loss / d conv_in output
+ *   (NDHWC [n][d][h][w][c], `dtype`, 16-byte aligned; c in {16, 32, 48, 64}): the transposed 3x3x3 conv with conv_in's fp32 master
+ *   weight [27 taps][c][cin] (cin in {1, 2}), zeros or circular padding, fp32 outputs [n][d][h][w] (ds may be NULL; needs cin == 2).
+ * K7b schedule_grad_sums: sums[n][2] = {sum dz x, sum dz eps} over the `per` elements of sample n - with alpha' and sigma' the gradient
+ *   of z_t = alpha x + sigma eps w.r.t. gamma_t.  eps == NULL: regenerated from its Philox counters (seed_eps, stream_eps, seed_step as
+ *   vdm_diffuse_pack: the same field).  Fixed-order two-stage reduction, no atomics (bit-reproducible).  per % 4 == 0; dz / x / eps
+ *   16-byte aligned; workspace as vdm_loss_terms. */
+int vdm_conv_in_dgrad(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
+                      float* dz, float* ds, void* stream);
+int vdm_schedule_grad_sums(const float* dz, const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps,
+                           const int32_t* seed_step, int n, int64_t per, float* sums, float* workspace, void* stream);
 
 /* ---- data path: crop + log-normalise + flip + permute on the device -----------------------------
  * Replaces the per-sample CPU DataLoader work of [REF src/dataset/CAMELS_3D_dataset.py:53-73] (AstroDataset.__getitem__) and

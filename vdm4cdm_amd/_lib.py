@@ -66,7 +66,7 @@ class AugmentSample(C.Structure):
 PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
-ABI_VERSION = 12                      # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 13                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -107,6 +107,7 @@ SIGNATURES = {
     "vdm_cond_table_fwd": (_i, [C.POINTER(CondMlp), _i, _i, _i, _p, _p, _p]),
     "vdm_cond_table_bwd": (_i, [C.POINTER(CondMlp), _i, _i, _i, _p, _i64, _p, _p, _p, _p]),
     "vdm_cond_table_step": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "vdm_cond_input_grad": (_i, [C.POINTER(CondMlp), _i, _i, _i, _p, _p, C.POINTER(_p), _p]),
     "vdm_augment_batch": (_i, [C.POINTER(AugmentChannel), _i, _i, _i, C.POINTER(AugmentSample), _i, _p]),
     "vdm_attn_split_heads": (_i, [_p, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p, _p]),
     "vdm_attn_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _f, _p, _p, _p]),
@@ -118,6 +119,8 @@ SIGNATURES = {
     "vdm_loss_terms": (_i, [_p, _p, _p, _p, _f, _p, _i, _i64, _p, _p, _p, _p]),
     "vdm_diffuse_pack": (_i, [_p, _p, _p, _u64, _u64, _p, _p, _p, _i, _i64, _i, _p, _p, _p]),
     "vdm_loss_terms_rng": (_i, [_p, _p, _u64, _u64, _p, _p, _u64, _u64, _p, _f, _p, _i, _i64, _p, _p, _p, _p]),
+    "vdm_conv_in_dgrad": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "vdm_schedule_grad_sums": (_i, [_p, _p, _p, _u64, _u64, _p, _i, _i64, _p, _p, _p]),
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_rows": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i64, _p]),

@@ -287,6 +287,46 @@ __global__ void __launch_bounds__(256) cond_table_bwd_params_kernel(const CondAr
     }
 }
 
+// K6i, input gradients: one block per (row, mlp), after the backward kernels above (reads dh1 from `scratch`, the input from `saved`).
+// d input[i] = sum_j dh1[j] W1[j][i]; a vector conditioning writes it ([rows][in_dim]), the sinusoidal t embedding folds it through
+// d/dt [sin(1000 t f_i), cos(1000 t f_i)] = 1000 f_i [cos, -sin] (saved values) into one dL/dt per row (fixed LDS tree: deterministic).
+struct CondDin {
+    float* p[COND_MAX];
+};
+
+__global__ void __launch_bounds__(256) cond_input_grad_kernel(const CondArgs a, const CondDin d) {
+    const int row = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    float* out = d.p[k];
+    if (!out) return;
+    const vdm_cond_mlp& m = a.m[k];
+    const float* sv = a.saved + saved_base(a, k) + (size_t)row * (m.in_dim + 3 * m.dim);
+    const float* sc = a.scratch + scratch_base(a, k) + (size_t)row * 2 * m.dim;
+    __shared__ float dh1[COND_MAXDIM];
+    __shared__ float red[256];
+    for (int j = tid; j < m.dim; j += 256) dh1[j] = sc[j];
+    __syncthreads();
+    float g = 0.f;
+    if (tid < m.in_dim)
+        for (int j = 0; j < m.dim; ++j) g = fmaf(dh1[j], m.w1[(size_t)j * m.in_dim + tid], g);
+    if (!m.sinusoid) {
+        if (tid < m.in_dim) out[(size_t)row * m.in_dim + tid] = g;
+        return;
+    }
+    float c = 0.f;
+    if (tid < m.in_dim) {
+        const int half = m.in_dim / 2, i = tid % half;
+        const float f = 1000.0f * expf(-9.210340371976184f * (float)i / (float)half);
+        c = tid < half ? g * f * sv[half + i] : -g * f * sv[i];
+    }
+    red[tid] = c;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) out[row] = red[0];
+}
+
 // sampler: table[b][w] = table_t[*step][w] + table_v[b][w]   (row gather by the device-side step counter)
 __global__ void __launch_bounds__(256) cond_table_step_kernel(const float* __restrict__ tt, const float* __restrict__ tv,
                                                              const int32_t* __restrict__ step, int rows, int width, float* __restrict__ out) {
@@ -364,6 +404,25 @@ extern "C" int vdm_cond_table_bwd(const vdm_cond_mlp* mlps, int n, int rows, int
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(cond_table_bwd_params_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, total);
     VDM_LAUNCH_CHECK("cond_table_bwd kernels");
+    return VDM_OK;
+}
+
+extern "C" int vdm_cond_input_grad(const vdm_cond_mlp* mlps, int n, int rows, int width, const float* saved, const float* scratch,
+                                   float* const* host_dinputs, void* stream) {
+    CondArgs a{};
+    int e = fill(a, mlps, n, rows, width, false);
+    if (e) return e;
+    VDM_REQUIRE(saved && scratch && host_dinputs, "cond_input_grad: NULL saved / scratch / dinputs");
+    VDM_REQUIRE(rows <= 65535, "cond_input_grad: at most 65535 rows per call (got %d)", rows);
+    CondDin d{};
+    for (int k = 0; k < n; ++k) {
+        VDM_REQUIRE(((uintptr_t)host_dinputs[k] & 3) == 0, "cond_input_grad: dinputs[%d] must be 4-byte aligned", k);
+        d.p[k] = host_dinputs[k];
+    }
+    a.saved = const_cast<float*>(saved);
+    a.scratch = const_cast<float*>(scratch);
+    hipLaunchKernelGGL(cond_input_grad_kernel, dim3(rows, n), dim3(256), 0, (hipStream_t)stream, a, d);
+    VDM_LAUNCH_CHECK("cond_input_grad_kernel");
     return VDM_OK;
 }
 

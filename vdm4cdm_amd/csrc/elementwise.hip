@@ -719,6 +719,35 @@ __global__ void __launch_bounds__(256) loss_terms_rng_kernel(const float* __rest
     }
 }
 
+// K7b: the per-sample sums of the learned schedule's gradient, part[block] = {sum dz x, sum dz eps} (dz = d loss / d z_t); eps read or
+// regenerated from the Philox counters of diffuse_pack_kernel (same (seed, stream id, element group) keying: the noise field is never
+// stored).  Vector form, 4 elements per thread; fold_partials_kernel sums the partials in a fixed order (bit-reproducible).
+__global__ void __launch_bounds__(256) schedule_grad_sums_kernel(const float* __restrict__ dz, const float* __restrict__ x,
+                                                                const float* __restrict__ eps, uint64_t seed0, uint64_t sid,
+                                                                const int32_t* __restrict__ seed_step, int64_t per, float* __restrict__ part,
+                                                                int blocks_per_n) {
+    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
+    const size_t base = (size_t)n * per;
+    const int64_t n4 = per >> 2;
+    const uint64_t seed = mix_seed(seed0, seed_step);
+    const float4* d4 = reinterpret_cast<const float4*>(dz + base);
+    const float4* x4 = reinterpret_cast<const float4*>(x + base);
+    const float4* e4 = eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
+    float acc[2] = {0.f, 0.f};
+    for (int64_t i = (int64_t)bn * 256 + threadIdx.x; i < n4; i += (int64_t)blocks_per_n * 256) {
+        const float4 dv = d4[i], xv = x4[i];
+        const float4 ev = e4 ? e4[i] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + i));
+        acc[0] += (dv.x * xv.x + dv.y * xv.y) + (dv.z * xv.z + dv.w * xv.w);
+        acc[1] += (dv.x * ev.x + dv.y * ev.y) + (dv.z * ev.z + dv.w * ev.w);
+    }
+    __shared__ float sm[8];
+    block_sum<2>(acc, sm);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.x * 2 + 0] = acc[0];
+        part[(size_t)blockIdx.x * 2 + 1] = acc[1];
+    }
+}
+
 // A product rounded on its own: the empty asm hides it from -ffp-contract=fast, which would otherwise fuse it into the add that consumes
 // it wherever the vectoriser happens not to pack the two products (no instruction is emitted).
 __device__ __forceinline__ float uncontracted_mul(float a, float b) {
@@ -1147,6 +1176,19 @@ extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t see
                        seed_eps0, stream_eps0, seed_step, s0a0, coef, per, workspace, d_eps_hat, bpn);
     hipLaunchKernelGGL(fold_partials_kernel, dim3(n * 3), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, bpn, 3, sums, 1);
     VDM_LAUNCH_CHECK("loss_terms_rng_kernel");
+    return VDM_OK;
+}
+
+extern "C" int vdm_schedule_grad_sums(const float* dz, const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps,
+                                      const int32_t* seed_step, int n, int64_t per, float* sums, float* workspace, void* stream) {
+    VDM_REQUIRE(dz && x && sums && workspace, "schedule_grad_sums: NULL pointer (dz, x, sums and workspace are required)");
+    VDM_REQUIRE(n > 0 && per > 0 && per % 4 == 0, "schedule_grad_sums: bad sizes n=%d per=%lld (per must be a multiple of 4)", n, (long long)per);
+    VDM_REQUIRE((((uintptr_t)dz | (uintptr_t)x | (uintptr_t)eps) & 15) == 0, "schedule_grad_sums: dz, x and eps must be 16-byte aligned");
+    const int bpn = bpn_for(per / 4, n);
+    hipLaunchKernelGGL(schedule_grad_sums_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, dz, x, eps, seed_eps, stream_eps, seed_step,
+                       per, workspace, bpn);
+    hipLaunchKernelGGL(fold_partials_kernel, dim3(n * 2), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, bpn, 2, sums, 0);
+    VDM_LAUNCH_CHECK("schedule_grad_sums_kernel");
     return VDM_OK;
 }
 

@@ -3,6 +3,8 @@
 * ``trainVDM3D*_..._thick_lowbatch.py <field_in> <field_out> <cropsize>`` ->  ``train_vdm3d(variant, argv)``
   (hyper-parameters per variant: /root/reference/trainVDM3D{,128,160,192,224}_c_c_from_field_name_thick_lowbatch.py:57-73,
   trainVDM3D_c_uc_from_field_name_thick_lowbatch.py:57-73; trainer settings :38-49).
+* ``train3D_c_c_from_field_name{,_160}.py <field_in> <field_out>`` (learned-linear schedule, chs [48, 96, 192, 384]) ->
+  ``train3d_c_c(variant, argv)``.
 * ``train_uc_uc_from_field_name.py <field_name>`` (2D, learned-linear schedule, circular padding; BASELINE config C1 runs it on
   CPU PyTorch) -> ``train_uc_uc(argv)`` (/root/reference/train_uc_uc_from_field_name.py:50-120).
 * ``trainSFM3D*_from_field_name*.py <field_in> <field_out> <cropsize>`` -> ``train_sfm3d(variant, argv)`` and the 2D
@@ -99,6 +101,53 @@ def train_vdm3d(variant, argv=None):
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
                       default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"),
                       experiment_name=name_pat.format(i=field_in, o=field_out, c=cropsize),
+                      n_val_sampling_steps=int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250)))
+    trainer.fit(model=vdm, datamodule=dm)
+    return trainer
+
+
+# train3D_c_c_from_field_name{,_160}.py: the wider network with the learned-linear schedule [REF train3D_c_c_from_field_name.py:
+# 28-68,110-129 and its _160 twin].  variant -> (cropsize, experiment-name pattern, slab thickness of the image); common settings below
+TRAIN3D_VARIANTS = {
+    "128": (128, "LH_c_uc_{i}_to_{o}", 16),
+    "160": (160, "LH_c_uc_{i}_to_{o}_160", 20),
+}
+TRAIN3D_COMMON = dict(dataset_name="CMD", suite_name="Astrid", set_name="LH", batch_size=2, chs=[48, 96, 192, 384], conditioning_values=6,
+                      norm_groups=8, dropout_prob=0.1, conv_padding_mode="zeros", noise_schedule="learned_linear", gamma_min=-13.3,
+                      gamma_max=13.3, val_check_interval=1000, every_n_train_steps=10_000, gradient_clip_val=0.5, learning_rate=3.0e-4)
+
+
+def train3d_c_c(variant, argv=None):
+    """train3D_c_c_from_field_name{,_160}.py <field_in> <field_out>: conditional 3D VDM with the learned-linear schedule
+    (gamma(t) = b + |w| t, trained with the network) and chs = [48, 96, 192, 384].  The experiment names are the reference's ("c_uc"
+    although the runs are conditional).  learning_rate: the reference passes none and mltools' default is not in the tree - LightVDM's
+    3e-4 [INFERRED]."""
+    from . import data, networks, vdm_model
+    from .trainer import Trainer
+    argv = sys.argv[1:] if argv is None else argv
+    if len(argv) != 2:
+        raise SystemExit("usage: <script> <field_in> <field_out>")
+    field_in, field_out = argv
+    cropsize, name_pat, thick = TRAIN3D_VARIANTS[variant]
+    c = TRAIN3D_COMMON
+    _seed_everything(42)
+
+    def return_func(fields, params):
+        return {"x": fields[1], "conditioning": fields[0], "conditioning_values": [params]}
+
+    dm = data.get_dataset(dataset_name=c["dataset_name"], suite_name=c["suite_name"], return_func=return_func, set_name=c["set_name"],
+                          z_name="z_0.0", channel_names=[field_in, field_out], stage="fit", batch_size=c["batch_size"], cropsize=cropsize,
+                          num_workers=12, mmap=False)
+    score_model = networks.CUNet(
+        shape=(1, cropsize, cropsize, cropsize), chs=c["chs"], s_conditioning_channels=1, v_conditioning_dims=[c["conditioning_values"]],
+        t_conditioning=True, norm_groups=c["norm_groups"], mid_attn=False, dropout_prob=c["dropout_prob"],
+        conv_padding_mode=c["conv_padding_mode"], n_attention_heads=4, backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
+    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, True), gamma_min=c["gamma_min"],
+                             gamma_max=c["gamma_max"], noise_schedule=c["noise_schedule"], learning_rate=c["learning_rate"])
+    trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=c["val_check_interval"],
+                      gradient_clip_val=c["gradient_clip_val"], every_n_train_steps=c["every_n_train_steps"],
+                      default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"),
+                      experiment_name=name_pat.format(i=field_in, o=field_out),
                       n_val_sampling_steps=int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250)))
     trainer.fit(model=vdm, datamodule=dm)
     return trainer

@@ -621,14 +621,23 @@ class CondTable:
         check(L.vdm_cond_table_fwd(arr, len(self.specs), self.rows, self.width, _p(table), _p(self.saved), _s()), "vdm_cond_table_fwd")
         return table
 
-    def backward(self, dtable, grads, dbias=None):
-        """grads: list of dicts {w1, b1, w2, b2, wproj} of fp32 views that receive the parameter gradients (plain stores)."""
+    def backward(self, dtable, grads, dbias=None, dinputs=None):
+        """grads: list of dicts {w1, b1, w2, b2, wproj} of fp32 views that receive the parameter gradients (plain stores).
+        dinputs (optional): one fp32 tensor or None per spec, the gradient of its input (K6i, vdm_cond_input_grad): [rows] for the
+        sinusoidal t embedding (dL/dt), [rows, in_dim] for a vector conditioning."""
         L = _lib.lib()
         assert self.saved is not None and dtable.dtype == torch.float32 and dtable.stride(1) == 1 and dtable.shape[0] == self.rows
         arr = self._descs(grads)
         scratch = torch.empty(L.vdm_cond_bwd_scratch_floats(arr, len(self.specs), self.rows, self.width), dtype=torch.float32, device=dtable.device)
         check(L.vdm_cond_table_bwd(arr, len(self.specs), self.rows, self.width, _p(dtable), dtable.stride(0), _p(self.saved), _p(scratch),
                                    _p(dbias), _s()), "vdm_cond_table_bwd")
+        if dinputs is not None:
+            assert len(dinputs) == len(self.specs)
+            for sp, d in zip(self.specs, dinputs):
+                assert d is None or (d.dtype == torch.float32 and d.is_contiguous() and tuple(d.shape) == tuple(sp["input"].shape))
+            ptrs = (C.c_void_p * len(self.specs))(*[_p(d) for d in dinputs])
+            check(L.vdm_cond_input_grad(arr, len(self.specs), self.rows, self.width, _p(self.saved), _p(scratch), ptrs, _s()),
+                  "vdm_cond_input_grad")
         self.saved = None
 
 
@@ -750,6 +759,33 @@ def diffuse_pack(x, s_cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, 
     check(L.vdm_diffuse_pack(_p(x), _p(s_cond), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per, dt_id(dtype),
                              _p(z), _p(packed), _s()), "vdm_diffuse_pack")
     return z, packed
+
+
+def conv_in_dgrad(dh, weight, cin, circular, want_s):
+    """K1t (vdm_conv_in_dgrad): the gradient of conv_in's input channels from dh = d loss / d conv_in output (NDHWC [N, D, H, W, C]).
+    weight: conv_in's fp32 master weight [27, C, cin].  Returns (dz, ds or None), fp32 [N, D, H, W]."""
+    L = _lib.lib()
+    _contig(dh, weight)
+    n, d, h, w, c = dh.shape
+    assert weight.dtype == torch.float32 and tuple(weight.shape) == (27, c, cin)
+    dz = torch.empty((n, d, h, w), dtype=torch.float32, device=dh.device)
+    ds = torch.empty_like(dz) if want_s else None
+    check(L.vdm_conv_in_dgrad(_p(dh), n, d, h, w, c, dt_id(dh.dtype), _lib.PAD_CIRCULAR if circular else _lib.PAD_ZEROS, _p(weight), cin,
+                              _p(dz), _p(ds), _s()), "vdm_conv_in_dgrad")
+    return dz, ds
+
+
+def schedule_grad_sums(dz, x, eps=None, seed=0, stream_id=0):
+    """K7b (vdm_schedule_grad_sums): [N, 2] fp32 = (sum dz x, sum dz eps) per sample; eps None: regenerated from Philox(seed, stream_id) -
+    the field diffuse_pack(..., seed, stream_id) drew."""
+    L = _lib.lib()
+    _contig(dz, x, eps)
+    n = x.shape[0]
+    assert dz.shape == x.shape and dz.dtype == x.dtype == torch.float32 and (eps is None or eps.shape == x.shape)
+    out = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+    check(L.vdm_schedule_grad_sums(_p(dz), _p(x), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), n, x.numel() // n, _p(out),
+                                   _p(_reduce_ws(x.device)), _s()), "vdm_schedule_grad_sums")
+    return out
 
 
 _red_ws = {}

@@ -76,7 +76,7 @@ def clip_grad_norm_flat_(params, max_norm, use_hip, want_norm=True):
         for g in big:
             ops.clip_scale_(g, acc, max_norm)
         if small:
-            coef = torch.clamp(max_norm / (acc.sqrt() + 1e-6), max=1.0)
+            coef = torch.clamp(max_norm / (acc.sqrt() + 1e-6), max=1.0).reshape(())     # (0-dim: also scales the schedule scalars' grads)
             for g in small:
                 g.mul_(coef.to(g.device))
         return acc.sqrt() if want_norm else None

@@ -5,7 +5,8 @@ into libvdm4cdm_hip.so on torch's current stream (so a caller can capture the wh
 a hipGraph).  PyTorch only allocates buffers and runs the tiny conditioning MLPs (R5).
 
 Tensors: activations NDHWC ``[N, D, H, W, C]`` in the compute dtype (bf16 or fp32); ``eps_hat`` fp32.
-Backward returns the gradient of the flat parameter vector and of the conditioning table.
+Backward returns the gradient of the flat parameter vector and of the conditioning table, and - only where autograd asks for them -
+the gradients of the inputs z, s_conditioning, t and v_conditionings (K1t, K6i).
 """
 import torch
 
@@ -451,10 +452,14 @@ class HipUNet:
             self.saved = (flat, xin, skips, coarse[::-1], h, st, a, table.shape)
         return eps.view(z.shape)
 
-    def backward(self, d_eps, cond=None):
+    def backward(self, d_eps, cond=None, want=None):
         """d_eps: fp32 [N, D, H, W].  Returns (grad of flat, grad of conditioning table).  cond: the hip_ops.CondTable whose
-        forward produced the table from this flat vector (its backward fills the conditioning parameters' gradients)."""
+        forward produced the table from this flat vector (its backward fills the conditioning parameters' gradients).
+        want = (z, s_cond, t, [v_k ...]) flags: the input gradients to return as a third element (dz, ds, dt, [dv_k ...]), None where
+        not asked (t / v need `cond`).  dz / ds take the unfused tail (the first block writes dh, then K1t), dt / dv K6i after the K6
+        backward; with want None the launches are those of the parameter-only backward."""
         net = self.net
+        want_x = want is not None and (want[0] or want[1])
         flat, xin, skips, coarse, h_last, st, a, tshape = self.saved
         self.saved = None
         L = len(net.chs)
@@ -501,16 +506,25 @@ class HipUNet:
                        skips[i], dh)
                 dh = self.down[i].dgrad(dh, residual=dskips[i])      # per-parity-class conv: no zero-dilated intermediate
             tail = None
-            if i == 0 and FUSED_GNB and self.res["downs.0.block"].skip1 is None and ops.gn_tail_ok(self.conv_in, self.res["downs.0.block"].saved[0]):
+            if (i == 0 and not want_x and FUSED_GNB and self.res["downs.0.block"].skip1 is None
+                    and ops.gn_tail_ok(self.conv_in, self.res["downs.0.block"].saved[0])):
                 tail = (self.conv_in, xin, GP("conv_in.weight"), GP("conv_in.bias"))      # the last apply pass + conv_in's weight gradient: one pass
             dh, _ = self.res[f"downs.{i}.block"].bwd(P, GP, dh, dtable, ss, tail=tail)
+        dz = ds = None
         if dh is not None:
             ss.run(lambda: self.conv_in.wgrad(xin, dh, GP("conv_in.weight"), GP("conv_in.bias")), xin, dh)
+            if want_x:                # K1t: the transposed conv_in on the main stream, next to its weight gradient on the side stream
+                dz, ds = ops.conv_in_dgrad(dh, P("conv_in.weight"), self.cin0, self.conv_in.circular, bool(want[1]) and self.cin0 == 2)
         # (the K6 backward only needs dtable - complete since the last block - and writes its own slice of gflat: it runs on the main
         # stream WHILE the side stream finishes the conv_in weight gradient, instead of behind the join)
+        dins = None
         if cond is not None:      # K6 backward: conditioning MLPs + projections + the conv1 biases (column sums of dtable), 3 launches
             grads = [{k: sp[k] for k in ("w1", "b1", "w2", "b2", "wproj")} for sp in net.cond_specs(None, [None] * len(net.v_conditioning_dims), gflat)]
-            cond.backward(dtable, grads, dbias=net.conv1_bias_all(gflat))
+            if want is not None and (want[2] or any(want[3])):      # (+ K6i: the inputs' gradients, one more launch)
+                flags = ([bool(want[2])] if net.t_conditioning else []) + [bool(f) for f in want[3]]
+                dins = [torch.empty(sp["input"].shape, dtype=torch.float32, device=flat.device) if f else None
+                        for sp, f in zip(cond.specs, flags)]
+            cond.backward(dtable, grads, dbias=net.conv1_bias_all(gflat), dinputs=dins)
         else:                     # conv1 biases: column sums of the conditioning-table gradient (same additive broadcast)
             net.conv1_bias_all(gflat).copy_(dtable.sum(0))
         ss.join()
@@ -520,7 +534,12 @@ class HipUNet:
             assert sum(hi - lo for lo, hi in done) == gflat.numel(), "gradient buckets do not cover the parameter vector"
             net.grad_synced = True
         self.net.weights_epoch += 1                  # the caller is about to change the parameters: re-pack at the next forward
-        return gflat, dtable
+        if want is None:
+            return gflat, dtable
+        nt = 1 if net.t_conditioning else 0
+        dt = dins[0] if (dins is not None and nt) else None
+        dvs = dins[nt:] if dins is not None else [None] * len(want[3])
+        return gflat, dtable, (dz, ds, dt, dvs)
 
 
 class _HipUNetFn(torch.autograd.Function):
@@ -551,8 +570,13 @@ class _HipUNetFn(torch.autograd.Function):
     def backward(ctx, d_eps):
         if not ctx.train:
             raise RuntimeError("HIP CUNet: backward requested but the forward ran without saving activations")
-        gflat, dtable = ctx.ex.backward(d_eps, ctx.cond)
-        return (gflat, dtable if ctx.table_grad else None, None, None, None, None, None, None, None) + (None,) * ctx.nvs
+        nd, has_cond = ctx.needs_input_grad, ctx.cond is not None       # (t / v reach the output only through the K6 table)
+        want = (nd[2], nd[3], nd[7] and has_cond, [nd[9 + j] and has_cond for j in range(ctx.nvs)])
+        if not (want[0] or want[1] or want[2] or any(want[3])):
+            gflat, dtable = ctx.ex.backward(d_eps, ctx.cond)
+            return (gflat, dtable if ctx.table_grad else None, None, None, None, None, None, None, None) + (None,) * ctx.nvs
+        gflat, dtable, (dz, ds, dt, dvs) = ctx.ex.backward(d_eps, ctx.cond, want=want)
+        return (gflat, dtable if ctx.table_grad else None, dz, ds, None, None, None, dt, None) + tuple(dvs)
 
 
 _seed_counter = [0]
@@ -589,7 +613,8 @@ def hip_unet_apply(net, x, s_conditioning, table=None, t=None, v_conditionings=N
             vs.append(v)
     # `train` here means "autograd records: keep the activations for backward"; the dropout probability follows net.training
     # (HipUNet.forward), exactly like nn.Dropout in the reference stack.
-    train = torch.is_grad_enabled() and (net.flat.requires_grad or (table is not None and table.requires_grad))
+    train = torch.is_grad_enabled() and (net.flat.requires_grad or (table is not None and table.requires_grad)
+                                         or any(a is not None and a.requires_grad for a in (z, s, t, *vs)))
     _seed_counter[0] += 1000
     # per-rank dropout masks under data parallelism: every rank calls seed_everything(42), so fold the rank in
     seed = (torch.initial_seed() + _seed_counter[0] + 0x9E3779B97F4A7C15 * _dist_rank()) & 0x7fffffffffffffff

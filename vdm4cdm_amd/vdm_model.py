@@ -68,6 +68,53 @@ class _ElboFn(torch.autograd.Function):
         return g * d, None, None, None, None, None, None, None
 
 
+class _LearnedDiffuseFn(torch.autograd.Function):
+    """z_t = alpha_n x + sigma_n eps of the learned schedule through the fused head (vdm_diffuse_pack: conv_in's packed input in the same
+    pass; eps None: drawn in the kernel from rng = (seed, stream)).  Backward: d alpha_n = sum dz x, d sigma_n = sum dz eps (K7b, eps read
+    or regenerated from the same counters); alpha / sigma are [B] tensors of torch autograd over (gamma_b, gamma_w)."""
+
+    @staticmethod
+    def forward(ctx, alpha, sigma, x, eps, rng, s_cond, dtype):
+        from . import hip_ops as ops
+        z_t, xin = ops.diffuse_pack(x, s_cond, alpha.detach().contiguous(), sigma.detach().contiguous(), dtype, eps=eps, seed=rng[0],
+                                    stream_id=rng[1], want_z=True)
+        ctx.save_for_backward(x, eps)
+        ctx.rng = rng
+        ctx.mark_non_differentiable(xin)
+        return z_t, xin
+
+    @staticmethod
+    def backward(ctx, dz, _):
+        from . import hip_ops as ops
+        x, eps = ctx.saved_tensors
+        if dz is None:
+            return (None,) * 7
+        sums = ops.schedule_grad_sums(dz.contiguous(), x, eps, *ctx.rng)
+        return sums[:, 0], sums[:, 1], None, None, None, None, None
+
+
+class _LearnedElboFn(torch.autograd.Function):
+    """K8 for the learned schedule: (diffusion loss 0.5 sum_n coef_n S_n, sums [B, 3]).  coef_n = |w| bpd / B is an input, so that
+    d loss / d coef_n = S_n / 2 reaches gamma_w (the diffusion weight gamma'(t) = |w|).  The kernel runs with sigma0/alpha0 = 1:
+    sums[:, 2] = sum eps0^2, which the reconstruction term scales by e^{gamma(0)} (= (sigma0/alpha0)^2) in torch."""
+
+    @staticmethod
+    def forward(ctx, eps_hat, coef, x, eps, eps0, rng):
+        from . import hip_ops as ops
+        c = coef.detach().contiguous()
+        d = torch.empty_like(eps_hat)
+        sums = torch.zeros(x.shape[0], 3, device=x.device)
+        ops.loss_terms(x, eps, eps_hat.contiguous(), eps0, 1.0, c, sums, d, rng=rng)
+        ctx.save_for_backward(d, sums)
+        ctx.mark_non_differentiable(sums)
+        return 0.5 * (c * sums[:, 0]).sum(), sums
+
+    @staticmethod
+    def backward(ctx, g, _):
+        d, sums = ctx.saved_tensors
+        return g * d, 0.5 * g * sums[:, 0], None, None, None, None
+
+
 class VDM(nn.Module):
     def __init__(self, score_model, noise_schedule="fixed_linear", gamma_min=-13.3, gamma_max=13.3,
                  antithetic_time_sampling=True, data_noise=DATA_NOISE, w_cfg=None):
@@ -164,6 +211,8 @@ class VDM(nn.Module):
         bpd = 1.0 / (numel * math.log(2.0))
         x = x.to(torch.float32).contiguous()
         hip = self._hip(x)
+        if hip and self.noise_schedule == "learned_linear":
+            return self._hip_learned_loss(x, times, eps, eps0, numel, bpd, kwargs)
         if not hip:
             if times is None:
                 times = self.sample_times(B, x.device)
@@ -177,10 +226,7 @@ class VDM(nn.Module):
         bc = (B,) + (1,) * (x.dim() - 1)
         if hip:
             from . import hip_ops as ops
-            if self.noise_schedule != "fixed_linear":
-                raise NotImplementedError("HIP training path supports noise_schedule='fixed_linear' (all 3D scripts); "
-                                          "'learned_linear' needs d loss / d z_t which the HIP backward does not emit")
-            rank, world = self._rank_world()               # (Philox stream id = 2*rank + {1,2}: different noise fields per rank)
+            rank, world = self._rank_world()              # (Philox stream id = 2*rank + {1,2}: different noise fields per rank)
             # Fused head: with no noise supplied, eps and eps0 are never materialised - K7 draws eps from its Philox
             # counters while it forms z_t and writes conv_in's packed input in the same pass, K8 regenerates both fields from the same
             # counters.  The host draws the two seeds exactly as the unfused path does (same generator state -> same noise fields).
@@ -248,6 +294,50 @@ class VDM(nn.Module):
         loss = diff + latent + recons
         metrics = {"elbo": loss.detach(), "diffusion_loss": diff.detach(), "latent_loss": latent.detach(),
                    "reconstruction_loss": recons.detach()}
+        return loss, metrics
+
+    def _hip_learned_loss(self, x, times, eps, eps0, numel, bpd, kwargs):
+        """get_loss of noise_schedule="learned_linear" on the HIP backend.  The activation-sized work is the fixed-linear path's kernels
+        (fused head K7, K8) plus the network's input gradients (K1t dz, K6i dL/dt_norm) and K7b; the [B]-sized scalar side - gamma_t,
+        alpha_t, sigma_t, t_norm, the diffusion weight |w| and the latent / reconstruction terms - is torch autograd over (gamma_b,
+        gamma_w), in fp64 where the latent term cancels.  No host synchronisation."""
+        from . import hip_ops as ops
+        B, dev, sm = x.shape[0], x.device, self.score_model
+        assert x.dim() == 5 and numel % 4 == 0, "the HIP learned-linear step needs 3D cubes with a multiple of 4 voxels"
+        rank, world = self._rank_world()
+        # noise: the seeds are drawn as on the fixed-linear path; a supplied field is read, a missing one drawn in the kernels
+        rng_e = (noise_seed(), 2 * rank + 1) if eps is None else (0, 0)
+        rng_0 = (noise_seed(), 2 * rank + 2) if eps0 is None else (0, 0)
+        if times is None and self.antithetic_time_sampling:          # the fixed path's time grid (stratified over the global batch)
+            u0 = torch.rand(1, device=dev, generator=train_generator(dev))
+            times = ops.train_scalars(B, dev, rank, world, self.gamma_min, self.gamma_max, bpd / B, u0=u0)[0]
+        elif times is None:
+            times = self.sample_times(B, dev)
+        times = times.to(device=dev, dtype=torch.float32).reshape(B)
+        wabs = self.gamma_w.abs()
+        g_t = self.gamma_b + wabs * times
+        t_norm = (g_t - self.gamma_min) / (self.gamma_max - self.gamma_min)
+        s_c = kwargs.get("s_conditioning") if sm.s_conditioning_channels else None
+        if s_c is not None:
+            s_c = s_c.to(device=dev, dtype=torch.float32).expand(x.shape).contiguous()
+        dt = torch.bfloat16 if sm.precision == "bf16" else torch.float32
+        z_t, xin = _LearnedDiffuseFn.apply(self.alpha(g_t), self.sigma(g_t), x, None if eps is None else eps.contiguous(), rng_e, s_c, dt)
+        if self.w_cfg is None or self.training:
+            eps_hat = sm(z_t, t=t_norm, _packed_input=xin, **kwargs)
+        else:
+            eps_hat = self.get_pred_noise(z_t, g_t, **kwargs)
+        coef = (wabs * (bpd / B)).expand(B)                          # 2 w_n = gamma'(t) bpd / B
+        diff, sums = _LearnedElboFn.apply(eps_hat, coef, x, None if eps is None else eps.contiguous(),
+                                          None if eps0 is None else eps0.contiguous(), (rng_e, rng_0))
+        g0 = self.gamma_b.double()
+        var1 = torch.sigmoid(g0 + self.gamma_w.double().abs())      # (fp64: var1 - log(var1) - 1 ~ 1e-12 cancels in fp32)
+        s = sums.double()
+        latent = (0.5 * (numel * (var1 - torch.log(var1) - 1.0) + (1.0 - var1) * s[:, 1])).mean() * bpd
+        dn = self.data_noise
+        recons = (0.5 * torch.exp(g0) * s[:, 2] / dn ** 2 + numel * (math.log(dn) + 0.5 * math.log(2 * math.pi))).mean() * bpd
+        loss = diff + (latent + recons).float()
+        metrics = {"elbo": loss.detach(), "diffusion_loss": diff.detach(), "latent_loss": latent.detach().float(),
+                   "reconstruction_loss": recons.detach().float()}
         return loss, metrics
 
     # ---------------------------------------------------------------- sampler (D12)
