@@ -277,7 +277,11 @@ int vdm_diffuse(const float* x, const float* eps, const float* alpha, const floa
                 float* z_t, void* stream);
 /* sums[n][3] += {sum (eps-eps_hat)^2, sum x^2, sum (x - z0r)^2} with z0r = x + (sigma0/alpha0) eps0;
  * d_eps_hat = coef[n] * (eps_hat - eps)   (coef folds bpd * gamma'(t) / B).  Caller zeroes sums. */
-/* workspace: >= 2048 * 3 floats (per-workgroup partials, folded in a fixed order: the loss is bit-reproducible). */
+/* workspace: VDM_REDUCE_WS_ROWS * 3 floats (per-workgroup partials, one row per block, folded in a fixed order: the loss is
+ * bit-reproducible).  Its size is not an argument: the entries that write partials (vdm_loss_terms, vdm_loss_terms_rng,
+ * vdm_schedule_grad_sums) launch at most max(1, VDM_REDUCE_WS_ROWS / n) blocks per sample and therefore refuse
+ * n > VDM_REDUCE_WS_ROWS. */
+#define VDM_REDUCE_WS_ROWS 2048
 int vdm_loss_terms(const float* x, const float* eps, const float* eps_hat, const float* eps0, float sigma0_over_alpha0,
                    const float* coef, int n, int64_t per, float* sums, float* d_eps_hat, float* workspace, void* stream);
 
@@ -304,7 +308,7 @@ int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t seed_eps, uint
  * K7b schedule_grad_sums: sums[n][2] = {sum dz x, sum dz eps} over the `per` elements of sample n - with alpha' and sigma' the gradient
  *   of z_t = alpha x + sigma eps w.r.t. gamma_t.  eps == NULL: regenerated from its Philox counters (seed_eps, stream_eps, seed_step as
  *   vdm_diffuse_pack: the same field).  Fixed-order two-stage reduction, no atomics (bit-reproducible).  per % 4 == 0; dz / x / eps
- *   16-byte aligned; workspace as vdm_loss_terms. */
+ *   16-byte aligned; workspace as vdm_loss_terms (VDM_REDUCE_WS_ROWS * 3 floats, n <= VDM_REDUCE_WS_ROWS). */
 int vdm_conv_in_dgrad(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
                       float* dz, float* ds, void* stream);
 int vdm_schedule_grad_sums(const float* dz, const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps,

@@ -70,6 +70,19 @@ def test_schedule_grad_sums_argument_errors(hip_lib):
     assert call(eps=8196) == -1 and b"aligned" in L.vdm_last_error()
 
 
+def test_reduction_entries_refuse_more_samples_than_workspace_rows(hip_lib):
+    """The two-stage reductions write one partial row per block into a workspace of 2048 rows whose size the C ABI never sees; with more
+    than 2048 samples even one block per sample overruns it, so the three entries refuse (before any launch)."""
+    L = hip_lib
+    for n in (2049, 100000):
+        assert L.vdm_schedule_grad_sums(4096, 8192, None, 1, 1, None, n, 64, 4096, 4096, None) == -1
+        assert b"schedule_grad_sums: at most 2048 samples" in L.vdm_last_error()
+        assert L.vdm_loss_terms(4096, 4096, 4096, 4096, 1.0, 4096, n, 64, 4096, 4096, 4096, None) == -1
+        assert b"loss_terms: at most 2048 samples" in L.vdm_last_error()
+        assert L.vdm_loss_terms_rng(4096, None, 1, 1, 4096, None, 2, 2, None, 1.0, 4096, n, 64, 4096, 4096, 4096, None) == -1
+        assert b"loss_terms_rng: at most 2048 samples" in L.vdm_last_error()
+
+
 def test_cond_input_grad_argument_errors(hip_lib):
     from vdm4cdm_amd._lib import CondMlp
     L = hip_lib

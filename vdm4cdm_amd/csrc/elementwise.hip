@@ -1120,9 +1120,11 @@ extern "C" int vdm_pack_input(const float* a, const float* b, int64_t nvox, int 
     return VDM_OK;
 }
 
+// blocks per sample of the two-stage reductions: bpn * n <= VDM_REDUCE_WS_ROWS partial rows as long as n <= VDM_REDUCE_WS_ROWS (the entries
+// that write partials require it: the workspace's size is not part of their arguments)
 static int bpn_for(int64_t per, int n) {
     int64_t b = (per + 256 * 16 - 1) / (256 * 16);
-    int64_t cap = 2048 / (n > 0 ? n : 1);
+    int64_t cap = VDM_REDUCE_WS_ROWS / (n > 0 ? n : 1);
     if (cap < 1) cap = 1;
     if (b > cap) b = cap;
     if (b < 1) b = 1;
@@ -1141,6 +1143,8 @@ extern "C" int vdm_diffuse(const float* x, const float* eps, const float* alpha,
 extern "C" int vdm_loss_terms(const float* x, const float* eps, const float* eps_hat, const float* eps0, float s0a0, const float* coef,
                               int n, int64_t per, float* sums, float* d_eps_hat, float* workspace, void* stream) {
     VDM_REQUIRE(x && eps && eps_hat && eps0 && coef && sums && d_eps_hat && workspace && n > 0 && per > 0, "loss_terms: bad arguments");
+    VDM_REQUIRE(n <= VDM_REDUCE_WS_ROWS, "loss_terms: at most %d samples per call (got %d): the workspace holds one partial row per block",
+                VDM_REDUCE_WS_ROWS, n);
     const int bpn = bpn_for(per, n);
     hipLaunchKernelGGL(loss_terms_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, x, eps, eps_hat, eps0, s0a0, coef, per, workspace,
                        d_eps_hat, bpn);
@@ -1171,6 +1175,8 @@ extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t see
                                   const float* coef, int n, int64_t per, float* sums, float* d_eps_hat, float* workspace, void* stream) {
     VDM_REQUIRE(x && eps_hat && coef && sums && d_eps_hat && workspace && n > 0 && per > 0 && per % 4 == 0,
                 "loss_terms_rng: bad arguments (per must be a multiple of 4)");
+    VDM_REQUIRE(n <= VDM_REDUCE_WS_ROWS, "loss_terms_rng: at most %d samples per call (got %d): the workspace holds one partial row per block",
+                VDM_REDUCE_WS_ROWS, n);
     const int bpn = bpn_for(per / 4, n);
     hipLaunchKernelGGL(loss_terms_rng_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, x, eps, seed_eps, stream_eps, eps_hat, eps0,
                        seed_eps0, stream_eps0, seed_step, s0a0, coef, per, workspace, d_eps_hat, bpn);
@@ -1184,6 +1190,8 @@ extern "C" int vdm_schedule_grad_sums(const float* dz, const float* x, const flo
     VDM_REQUIRE(dz && x && sums && workspace, "schedule_grad_sums: NULL pointer (dz, x, sums and workspace are required)");
     VDM_REQUIRE(n > 0 && per > 0 && per % 4 == 0, "schedule_grad_sums: bad sizes n=%d per=%lld (per must be a multiple of 4)", n, (long long)per);
     VDM_REQUIRE((((uintptr_t)dz | (uintptr_t)x | (uintptr_t)eps) & 15) == 0, "schedule_grad_sums: dz, x and eps must be 16-byte aligned");
+    VDM_REQUIRE(n <= VDM_REDUCE_WS_ROWS, "schedule_grad_sums: at most %d samples per call (got %d): the workspace holds one partial row per block",
+                VDM_REDUCE_WS_ROWS, n);
     const int bpn = bpn_for(per / 4, n);
     hipLaunchKernelGGL(schedule_grad_sums_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, dz, x, eps, seed_eps, stream_eps, seed_step,
                        per, workspace, bpn);
