@@ -29,23 +29,36 @@ def desc(**kw):
 
 
 def plan_everything(d):
-    """every host-only helper on one descriptor; the results only have to be consistent with each other"""
+    """every host-only helper on one descriptor; the results only have to be consistent with each other - and are: they all read
+    the one plan of the conv (csrc/conv_common.h plan_of), so layout, kernel family and tile count cannot drift apart"""
     global calls
+    variant = {}
     for mode in (0, 1):
         nbytes = L.vdm_conv_packed_bytes(d, mode)
         it = PackItem()
         buf = (C.c_char * 64)()
         st = L.vdm_conv_pack_plan(d, mode, C.addressof(buf), C.addressof(buf), C.byref(it))
+        variant[mode] = L.vdm_conv_kernel_variant(d, mode)
         if nbytes:
             assert st == 0 and it.elems * (4 if d.dtype == 0 else 2) == nbytes, (nbytes, it.elems)
+            # the packed layout is the class / tap-packed one exactly when the kernel of that direction is
+            assert it.variant in (0, 1, 2) and variant[mode] in (0, 1, 2, 3, 4), (it.variant, variant[mode])
+            assert (it.variant == 1) == (variant[mode] == 1) and (it.variant == 2) == (variant[mode] == 2), (mode, it.variant, variant[mode])
         else:
             assert st != 0 and L.vdm_last_error()
-        L.vdm_conv_kernel_variant(d, mode)
+            assert variant[mode] == -1
         calls += 3
     t1, t2 = L.vdm_conv_gn_tiles(d), L.vdm_conv_dgrad_gn_tiles(d)
     ws = L.vdm_conv_wgrad_workspace_bytes(d)
     assert t1 >= 0 and t2 >= 0 and ws >= 0
-    calls += 3
+    gn_ok = L.vdm_conv_fwd_gn_supported(d)
+    if L.vdm_conv_packed_bytes(d, 0):          # accepted descriptor
+        assert t1 > 0 and ws > 0, (t1, ws)
+        assert (t2 > 0) == (d.ksize == 3 and d.stride == 1 and not d.upsample), t2          # only those convs feed a GroupNorm backward
+        assert not gn_ok or variant[0] in (0, 3), variant          # GroupNorm prologue: generic kernel or its half-chunk form only
+    else:
+        assert t1 == 0 and t2 == 0 and not gn_ok
+    calls += 5
 
 
 # 1. the shapes of the network family, every (ksize, stride, upsample, dtype, pad) the product uses

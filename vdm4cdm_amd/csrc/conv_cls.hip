@@ -16,7 +16,7 @@ namespace vdm {
 // MODE_F: one workgroup = one class x one coarse tile, output scattered to the fine grid (stride 2).
 // MODE_B: one workgroup = one coarse tile; loops over the 8 classes, re-staging the class sub-grid G_p[c] = dOut[2c+p]
 //         (source stride 2) and accumulating in registers.
-// The packed weights hold 64 (class, entry) slots per (chunk, K-block); pack_weights_cls_kernel sums the master taps of
+// The packed weights hold 64 (class, entry) slots per (chunk, K-block); pack_value (conv_api.hip) sums the master taps of
 // each slot's mask (and transposes for the gradient modes).
 // ---------------------------------------------------------------------------------------------
 
@@ -234,14 +234,13 @@ static int launch_cls(const ClsArgs& ca, int nc, int mode_b, hipStream_t s) {
     }
 }
 
-// x: staged tensor (K channels), out: O channels.  cd/ch/cw: coarse dims.
-int run_cls(const vdm_conv_desc* d, int kind, const void* x, const void* w, const float* bias, const void* res, void* out,
-                   int cd, int ch, int cw, hipStream_t s, float* gn_partials) {
-    const int dgrad = kind != CLS_UP_FWD;
-    const Plan p = plan_of(d, dgrad);
+// x: staged tensor (K channels), out: O channels; the plan's grid is the coarse one the classes tile
+int run_cls(const vdm_conv_desc* d, const Plan& p, const void* x, const void* w, const float* bias, const void* res, void* out,
+            hipStream_t s, float* gn_partials) {
+    const int cd = p.Dz, ch = p.Dy, cw = p.Dx;
     ClsArgs ca{};
     ClsMasks masks;
-    build_cls(kind, ca.t, masks);
+    build_cls(p.cls_kind, ca.t, masks);
     ConvArgs& a = ca.c;
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.out = out; a.gnp = gn_partials;
     a.N = d->n; a.Dz = cd; a.Dy = ch; a.Dx = cw;
@@ -249,7 +248,7 @@ int run_cls(const vdm_conv_desc* d, int kind, const void* x, const void* w, cons
     a.circular = d->pad_mode == VDM_PAD_CIRCULAR;
     a.Cin = p.K; a.CinStride = cpad(p.K, d->dtype); a.Cout = p.O;
     a.nchunks = p.nchunks; a.nkb = p.nkb;
-    const int mode_b = kind == CLS_UP_DGRAD;
+    const int mode_b = p.cls_kind == CLS_UP_DGRAD;
     ca.sDz = mode_b ? 2 * cd : cd; ca.sDy = mode_b ? 2 * ch : ch; ca.sDx = mode_b ? 2 * cw : cw;
     ca.oDz = mode_b ? cd : 2 * cd; ca.oDy = mode_b ? ch : 2 * ch; ca.oDx = mode_b ? cw : 2 * cw;
     if (d->dtype == VDM_F32) return launch_cls<float>(ca, p.nc, mode_b, s);

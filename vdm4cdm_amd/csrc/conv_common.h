@@ -1301,19 +1301,20 @@ static int validate(const vdm_conv_desc* d) {
     return VDM_OK;
 }
 
-struct Plan {           // derived launch parameters of one conv in one direction
-    int taps, nc, nchunks, nkb, O, K;
+// The host-side answer for one conv in one direction: packed-weight layout, kernel family, spatial tile and partial-tile count.
+// plan_of() (below the class tables) is the only place that decides any of it; the launchers, the weight packers and the planning
+// entry points of conv_api.hip read the plan.  A new kernel family, tile or layout is added there and nowhere else.
+struct Plan {
+    int taps, nc, nchunks, nkb, O, K;            // O output / K reduction channels of this direction; nc 16-channel tiles per chunk
+    int dtype, ks, stride, ups, out_f32;         // the conv as its kernel sees it (a dgrad is a stride-1 conv on the output grid)
+    int N, Dz, Dy, Dx;                           // tile index space (the coarse grid of an up-sampling conv)
+    int layout, cls_kind;                        // packed weights: VDM_CONV_VARIANT_GENERIC | _CLASS (of ClsKind cls_kind) | _KPACK
+    int family;                                  // kernel: VDM_CONV_VARIANT_*
+    int roll, wg8;                               // generic family, 4x8x16 tile: rolling-z kernel | eight waves (bit 0 plain, bit 1 folded GroupNorm backward)
+    int tz, ty;                                  // spatial tile (TX = 16)
+    int tiles;                                   // per-sample tiles of the GroupNorm partials [n][tiles][O][2]
+    size_t packed_bytes;
 };
-static Plan plan_of(const vdm_conv_desc* d, int dgrad) {
-    Plan p;
-    p.taps = d->ksize * d->ksize * d->ksize;
-    p.O = dgrad ? d->cin : d->cout;
-    p.K = dgrad ? d->cout : d->cin;
-    p.nc = nc_for(p.O, d->dtype);
-    p.nchunks = cdiv(p.O, p.nc * 16);
-    p.nkb = cdiv(p.K, kb_of(d->dtype));
-    return p;
-}
 
 static int cu_count();
 
@@ -1351,38 +1352,38 @@ static int cu_count() {                                   // of the current devi
 // everything at batch 1): smaller tiles so that more workgroups exist - a workgroup runs its K-blocks strictly one after the other
 // (stage, barrier, 27 taps), so a deep-level conv is bound by that serial chain unless co-resident workgroups overlap it:
 // 2x8x16 (46 KB LDS, 3 per CU) below 2 workgroups per CU, 1x8x16 / 1x4x16 when even those leave CUs empty.
-static void small_grid_tile(const ConvArgs& a, int& tz, int& ty) {
-    const long long per_sample = (long long)a.nchunks * a.N * cdiv(a.Dx, 16);
-    const long long tiles48 = per_sample * cdiv(a.Dz, 4) * cdiv(a.Dy, 8), tiles28 = per_sample * cdiv(a.Dz, 2) * cdiv(a.Dy, 8);
-    tz = 4; ty = 8;
+static void small_grid_tile(Plan& p) {
+    const long long per_sample = (long long)p.nchunks * p.N * cdiv(p.Dx, 16);
+    const long long tiles48 = per_sample * cdiv(p.Dz, 4) * cdiv(p.Dy, 8), tiles28 = per_sample * cdiv(p.Dz, 2) * cdiv(p.Dy, 8);
+    p.tz = 4; p.ty = 8;
     if (const char* f = getenv("VDM4CDM_FORCE_TZ")) {      // experiments: force the z extent of the tile (4 | 2 | 1)
-        tz = atoi(f);
-        if (tz == 1 || tz == 2 || tz == 4) return;
-        tz = 4;
+        p.tz = atoi(f);
+        if (p.tz == 1 || p.tz == 2 || p.tz == 4) return;
+        p.tz = 4;
     }
     if (tiles48 >= 2LL * cu_count()) return;
-    tz = 2;
+    p.tz = 2;
     if (tiles28 >= cu_count()) return;
-    tz = 1;
-    if (2 * tiles28 < cu_count()) ty = 4;
+    p.tz = 1;
+    if (2 * tiles28 < cu_count()) p.ty = 4;
 }
 
 // NC=4 conv with fewer than two workgroups per CU even on the small tiles: half-chunk workgroups (the NC=2 kernel on the same packed
 // weights; bf16 3x3x3 stride 1, not the up-sampling conv)
-static bool uses_split(const ConvArgs& a, int tz, int ty) {
-    const long long wgs = (long long)a.nchunks * a.N * cdiv(a.Dz, tz) * cdiv(a.Dy, ty) * cdiv(a.Dx, 16);
-    return tz <= 2 && wgs < 2LL * cu_count() && a.Cout % 64 == 0 && getenv("VDM4CDM_NO_SPLIT") == nullptr;
+static bool uses_split(const Plan& p) {
+    const long long wgs = (long long)p.nchunks * p.N * cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16);
+    return p.tz <= 2 && wgs < 2LL * cu_count() && p.O % 64 == 0 && getenv("VDM4CDM_NO_SPLIT") == nullptr;
 }
 
 // K-split kernel of the deepest levels (conv_fwd.hip, conv_ksplit_kernel): bf16 3x3x3 stride-1 convs with >= 4 K-blocks and 64-cout
-// chunks whose grid is small enough for small_grid_tile() to leave the 4x8x16 tile.  Takes the (tz, ty) small_grid_tile chose and
-// returns the tile the K-split kernel uses (1 x ty x 16; a 2x8x16 choice becomes 1x8x16).  VDM4CDM_KSPLIT: 0 off, 1 (default) only
+// chunks whose grid is small enough for small_grid_tile() to leave the 4x8x16 tile.  Turns the (tz, ty) small_grid_tile chose into
+// the tile the K-split kernel uses (1 x ty x 16; a 2x8x16 choice becomes 1x8x16).  VDM4CDM_KSPLIT: 0 off, 1 (default) only
 // where the generic choice was a 1 x ty x 16 tile (level 3 of the 128^3 network), 2 also the 2x8x16 grids (level 2: measured SLOWER
 // there - 0.078 vs 0.054 ms at batch 2 - one workgroup per CU loses more than the saved weight traffic gains).
-static bool ksplit_tile(const ConvArgs& a, int& tz, int& ty) {
+static bool ksplit_tile(Plan& p) {
     static const int level = getenv("VDM4CDM_KSPLIT") ? atoi(getenv("VDM4CDM_KSPLIT")) : 1;
-    if (level <= 0 || a.nkb < 4 || a.Cout % 64 != 0 || tz > 2 || (tz == 2 && level < 2)) return false;
-    if (tz == 2) { tz = 1; ty = 8; }
+    if (level <= 0 || p.nkb < 4 || p.O % 64 != 0 || p.tz > 2 || (p.tz == 2 && level < 2)) return false;
+    if (p.tz == 2) { p.tz = 1; p.ty = 8; }
     return true;
 }
 
@@ -1397,13 +1398,6 @@ static int s2_tile_z() {
 static int wgrad_wgs() {
     static const int v = getenv("VDM4CDM_WGRAD_WGS") ? atoi(getenv("VDM4CDM_WGRAD_WGS")) : 512;
     return v > 0 ? v : 512;
-}
-
-static bool uses_kpack(int dtype, int ks, int stride, int ups, int K, int O, int out_f32) {
-    return dtype == VDM_BF16 && ks == 3 && stride == 1 && !ups && K <= 8 && O <= 32 && !out_f32 && getenv("VDM4CDM_NO_KPACK") == nullptr;
-}
-static bool uses_kpack(const vdm_conv_desc* d, int dgrad) {
-    return uses_kpack(d->dtype, d->ksize, d->stride, d->upsample, dgrad ? d->cout : d->cin, dgrad ? d->cin : d->cout, dgrad ? 0 : d->out_f32);
 }
 
 // ---- class-conv tables -----------------------------------------------------------------------
@@ -1452,8 +1446,50 @@ static void build_cls(int kind, ClsTable& tab, ClsMasks& masks) {
     }
 }
 
-static bool uses_cls(const vdm_conv_desc* d, int dgrad) { return d->ksize == 3 && (d->upsample || (dgrad && d->stride == 2)); }
-static int cls_kind(const vdm_conv_desc* d, int dgrad) { return d->upsample ? (dgrad ? CLS_UP_DGRAD : CLS_UP_FWD) : CLS_S2_DGRAD; }
+static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed validate()
+    Plan p{};
+    p.taps = d->ksize * d->ksize * d->ksize;
+    p.O = dgrad ? d->cin : d->cout;
+    p.K = dgrad ? d->cout : d->cin;
+    p.nc = nc_for(p.O, d->dtype);
+    p.nchunks = cdiv(p.O, p.nc * 16);
+    p.nkb = cdiv(p.K, kb_of(d->dtype));
+    p.dtype = d->dtype; p.ks = d->ksize;
+    p.stride = dgrad ? 1 : d->stride; p.ups = dgrad ? 0 : d->upsample; p.out_f32 = dgrad ? 0 : d->out_f32;
+    p.N = d->n; p.Dz = d->od; p.Dy = d->oh; p.Dx = d->ow;
+    p.layout = p.family = VDM_CONV_VARIANT_GENERIC;
+    p.tz = 4; p.ty = 8;
+    size_t slots = (size_t)p.nkb * p.taps;                 // [64 lanes][16 B] weight fragments per chunk and cout tile
+    const bool bf16io = d->dtype == VDM_BF16 && !p.out_f32;
+    if (d->ksize == 3 && (d->upsample || (dgrad && d->stride == 2))) {      // per-parity-class kernel (conv_cls.hip): 4x8x16 tiles of the coarse grid
+        p.layout = p.family = VDM_CONV_VARIANT_CLASS;
+        p.cls_kind = d->upsample ? (dgrad ? CLS_UP_DGRAD : CLS_UP_FWD) : CLS_S2_DGRAD;
+        if (d->upsample) { p.Dz /= 2; p.Dy /= 2; p.Dx /= 2; }
+        slots = (size_t)p.nkb * 64;                         // 64 (class, entry) slots
+    } else if (bf16io && p.ks == 3 && p.stride == 1 && p.K <= 8 && p.O <= 32 && getenv("VDM4CDM_NO_KPACK") == nullptr) {
+        p.layout = p.family = VDM_CONV_VARIANT_KPACK;      // tap-packed kernel, 4x8x16
+        slots = 7;                                          // 7 groups of 4 taps
+    } else if (p.stride == 2) {
+        p.tz = s2_tile_z(); p.ty = 4;
+    } else if (p.ks == 3) {      // (fp32 storage too since round 4: on the bf16 pipe it is no longer MFMA-bound, small grids need small tiles)
+        small_grid_tile(p);
+        if (bf16io && p.nc == 4) {
+            if (ksplit_tile(p)) p.family = VDM_CONV_VARIANT_KSPLIT;
+            else if (uses_split(p)) p.family = VDM_CONV_VARIANT_SPLIT;
+        }
+        if (bf16io && p.nc == 2 && p.tz == 4) {            // (NC = 4 needs > 128 registers per wave: its accumulators alone are 64)
+            // rolling-z kernel: one K-block, large grid: persistent walk up z; VDM4CDM_ROLL=0 switches it off (A/B)
+            static const bool roll_on = getenv("VDM4CDM_ROLL") ? atoi(getenv("VDM4CDM_ROLL")) != 0 : true;
+            // VDM4CDM_WG8: bit mask of the kernel classes that run eight-wave workgroups on the 4x8x16 tile - 1: plain, 2: folded GroupNorm backward
+            static const int wg8_mask = getenv("VDM4CDM_WG8") ? atoi(getenv("VDM4CDM_WG8")) : 0;
+            p.roll = p.nkb == 1 && cdiv(p.Dz, 4) >= 4 && roll_on;
+            p.wg8 = p.roll ? 0 : (wg8_mask & 3);
+        }
+    }
+    p.tiles = cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16) * (p.cls_kind == CLS_UP_FWD && p.family == VDM_CONV_VARIANT_CLASS ? 8 : 1);
+    p.packed_bytes = (size_t)p.nchunks * slots * p.nc * 64 * 16;
+    return p;
+}
 
 static void fill_dims(ConvArgs& a, const vdm_conv_desc* d) {
     a.N = d->n; a.Dz = d->od; a.Dy = d->oh; a.Dx = d->ow;
@@ -1462,28 +1498,17 @@ static void fill_dims(ConvArgs& a, const vdm_conv_desc* d) {
     a.circular = d->pad_mode == VDM_PAD_CIRCULAR;
 }
 
-// spatial tile (TZ, TY; TX = 16) that vdm_conv_fwd will use for this conv - mirrors launch_fwd / launch_fwd_geo
-static void fwd_tile_shape(const ConvArgs& a, int dtype, int out_f32, int ks, int stride, int ups, int& tz, int& ty) {
-    tz = 4; ty = 8;
-    if (stride == 2) { tz = s2_tile_z(); ty = 4; return; }
-    if (uses_kpack(dtype, ks, stride, ups, a.Cin, a.Cout, out_f32)) return;
-    if (ks == 3) {
-        small_grid_tile(a, tz, ty);
-        if (dtype == VDM_BF16 && stride == 1 && !ups && !out_f32) ksplit_tile(a, tz, ty);
-    }
-}
-
 // launchers (defined in conv_fwd.hip / conv_cls.hip / conv_wgrad.hip)
-int launch_fwd(const ConvArgs& a, int dtype, int out_f32, int ks, int stride, int ups, int nc, hipStream_t s);
-int launch_fwd_gnb(const ConvArgs& a, int dtype, int nc, hipStream_t s);
-int launch_fwd_gnp(const ConvArgs& a, int out_f32, int nc, hipStream_t s);
+int launch_fwd(const ConvArgs& a, const Plan& p, hipStream_t s);
+int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s);
+int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s);
 // wgrad_thin.hip: weight gradient of conv_in / conv_out (one thin side)
 int wgrad_thin_mode(int dtype, int ksize, int stride, int upsample, int cin, int cout, bool want_bias, bool accumulate);
 size_t wgrad_thin_workspace_bytes(int n, int od, int oh, int ow, int cdense);
 int launch_wgrad_thin(int mode, const void* x, const void* dout, int n, int od, int oh, int ow, int cin, int cout, int circular, float* dw,
                       float* dbias, void* workspace, size_t workspace_bytes, hipStream_t s);
-int run_cls(const vdm_conv_desc* d, int kind, const void* x, const void* w, const float* bias, const void* res, void* out,
-            int cd, int ch, int cw, hipStream_t s, float* gn_partials = nullptr);
+int run_cls(const vdm_conv_desc* d, const Plan& p, const void* x, const void* w, const float* bias, const void* res, void* out,
+            hipStream_t s, float* gn_partials = nullptr);
 // conv_wgrad.hip: fixed-order fold of the P per-workgroup slabs [P][27][32][32] (+ [P][32] bias partials) of conv_dgw.hip
 int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float* dbias, int P, int accumulate, hipStream_t s);
 int launch_wgrad_any(const WgradArgs& w, float* dw, float* db, int acc, int cout, int cin, int ks, int stride, int ups, size_t ws,

@@ -432,17 +432,7 @@ static int launch_fwd_cfg(const ConvArgs& a0, hipStream_t s) {
     return VDM_OK;
 }
 
-// VDM4CDM_WG8: bit mask of the NC = 2 kernel classes that run eight-wave workgroups on the 4x8x16 tile - 1: plain, 2: folded GroupNorm backward
-static bool wg8_enabled(int nc, bool gnb) {
-    static const int mask = getenv("VDM4CDM_WG8") ? atoi(getenv("VDM4CDM_WG8")) : 0;
-    return nc == 2 && ((mask >> (gnb ? 1 : 0)) & 1);
-}
-
-// rolling-z kernel: bf16, one K-block, 3x3x3 stride 1, bf16 output, 4x8x16 steps; VDM4CDM_ROLL=0 switches it off (A/B)
-static bool roll_enabled() {
-    static const bool on = getenv("VDM4CDM_ROLL") ? atoi(getenv("VDM4CDM_ROLL")) != 0 : true;
-    return on;
-}
+// rolling-z kernel: bf16, one K-block, 3x3x3 stride 1, bf16 output, 4x8x16 steps (Plan::roll)
 template <typename T, int NC, bool GNB>
 static int launch_roll(const ConvArgs& a0, hipStream_t s) {
     using G = Geo<3, 1, 4, 8>;
@@ -490,31 +480,28 @@ static int launch_ksplit(const ConvArgs& a0, hipStream_t s) {
     return VDM_OK;
 }
 
+// plan -> template instantiation.  Every run-time choice is plan_of()'s; the `if constexpr` guards only bound the set of built kernels.
 template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, bool GNB = false, bool GNP = false>
-static int launch_fwd_geo(const ConvArgs& a, hipStream_t s) {
+static int launch_fwd_geo(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    const int tz = p.tz, ty = p.ty;
     if constexpr (STRIDE == 2)
-        return s2_tile_z() == 1 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 4>(a, s);
-    else if constexpr (KS == 3) {      // (fp32 storage too since round 4: on the bf16 pipe it is no longer MFMA-bound, small grids need small tiles)
-        int tz, ty;
-        small_grid_tile(a, tz, ty);
+        return tz == 1 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 4>(a, s);
+    else if constexpr (KS == 3) {
         if constexpr (NC == 4 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2) {
-            if (ksplit_tile(a, tz, ty)) {
+            if (p.family == VDM_CONV_VARIANT_KSPLIT) {
                 if constexpr (GNP) { set_error("conv_fwd_gn: the K-split kernel has no GroupNorm prologue (vdm_conv_fwd_gn_supported)"); return VDM_ERR_UNSUPPORTED; }
                 else return ty == 4 ? launch_ksplit<T, TO, 4, 4, GNB>(a, s) : launch_ksplit<T, TO, 4, 8, GNB>(a, s);
             }
-            if (uses_split(a, tz, ty)) {
+            if (p.family == VDM_CONV_VARIANT_SPLIT) {
                 if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 4, true, GNB, GNP>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 8, true, GNB, GNP>(a, s);
                 return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 2, 8, true, GNB, GNP>(a, s);
             }
         }
         if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4, false, GNB, GNP>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 8, false, GNB, GNP>(a, s);
         if (tz == 2) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 8, false, GNB, GNP>(a, s);
-        if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2 && !GNP) {      // one K-block, large grid: persistent walk up z
-            if (a.nkb == 1 && cdiv(a.Dz, 4) >= 4 && roll_enabled()) return launch_roll<T, NC, GNB>(a, s);
-        }
-        if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2 && !GNP) {      // large grids: eight waves share the 4x8x16 tile
-            // (NC = 4 needs > 128 registers per wave: its accumulators alone are 64)
-            if (wg8_enabled(NC, GNB)) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP, 8>(a, s);
+        if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2 && !GNP) {      // (the prologue runs on the plain 4x8x16 kernel)
+            if (p.roll) return launch_roll<T, NC, GNB>(a, s);
+            if ((p.wg8 >> (GNB ? 1 : 0)) & 1) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP, 8>(a, s);
         }
         return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP>(a, s);
     } else
@@ -522,22 +509,21 @@ static int launch_fwd_geo(const ConvArgs& a, hipStream_t s) {
 }
 
 template <typename T, typename TO, int KS, int STRIDE, int UPS, bool GNB = false, bool GNP = false>
-static int launch_fwd_nc(const ConvArgs& a, int nc, hipStream_t s) {
-    switch (nc) {
-        case 1: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 1, GNB, GNP>(a, s);
-        case 2: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 2, GNB, GNP>(a, s);
-        default: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 4, GNB, GNP>(a, s);
+static int launch_fwd_nc(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    switch (p.nc) {
+        case 1: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 1, GNB, GNP>(a, p, s);
+        case 2: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 2, GNB, GNP>(a, p, s);
+        default: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 4, GNB, GNP>(a, p, s);
     }
 }
 
 template <typename T, typename TO>
-static int launch_fwd_variant(const ConvArgs& a, int ks, int stride, int ups, int nc, hipStream_t s) {
-    if (ks == 1) return launch_fwd_nc<T, TO, 1, 1, 0>(a, nc, s);
-    if (stride == 2) return launch_fwd_nc<T, TO, 3, 2, 0>(a, nc, s);
-    if (ups) return launch_fwd_nc<T, TO, 3, 1, 1>(a, nc, s);
-    return launch_fwd_nc<T, TO, 3, 1, 0>(a, nc, s);
+static int launch_fwd_variant(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    if (p.ks == 1) return launch_fwd_nc<T, TO, 1, 1, 0>(a, p, s);
+    if (p.stride == 2) return launch_fwd_nc<T, TO, 3, 2, 0>(a, p, s);
+    if (p.ups) return launch_fwd_nc<T, TO, 3, 1, 1>(a, p, s);
+    return launch_fwd_nc<T, TO, 3, 1, 0>(a, p, s);
 }
-
 
 template <int NC, bool GNB = false>
 static int launch_kpack(const ConvArgs& a0, hipStream_t s) {
@@ -553,30 +539,30 @@ static int launch_kpack(const ConvArgs& a0, hipStream_t s) {
     return VDM_OK;
 }
 
-int launch_fwd(const ConvArgs& a, int dtype, int out_f32, int ks, int stride, int ups, int nc, hipStream_t s) {
-    if (uses_kpack(dtype, ks, stride, ups, a.Cin, a.Cout, out_f32)) return nc == 1 ? launch_kpack<1>(a, s) : launch_kpack<2>(a, s);
-    if (dtype == VDM_F32) return launch_fwd_variant<float, float>(a, ks, stride, ups, nc, s);
-    if (out_f32) {
-        if (!(ks == 3 && stride == 1 && !ups && nc == 1)) {
+int launch_fwd(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    if (p.family == VDM_CONV_VARIANT_KPACK) return p.nc == 1 ? launch_kpack<1>(a, s) : launch_kpack<2>(a, s);
+    if (p.dtype == VDM_F32) return launch_fwd_variant<float, float>(a, p, s);
+    if (p.out_f32) {
+        if (!(p.ks == 3 && p.stride == 1 && !p.ups && p.nc == 1)) {
             set_error("conv: out_f32 with bf16 input is only built for ksize 3, stride 1, cout <= 16");
             return VDM_ERR_UNSUPPORTED;
         }
-        return launch_fwd_geo<bf16_t, float, 3, 1, 0, 1>(a, s);
+        return launch_fwd_geo<bf16_t, float, 3, 1, 0, 1>(a, p, s);
     }
-    return launch_fwd_variant<bf16_t, bf16_t>(a, ks, stride, ups, nc, s);
+    return launch_fwd_variant<bf16_t, bf16_t>(a, p, s);
 }
 
 // dgrad of a 3x3x3 stride-1 conv with the GroupNorm+SiLU backward reduction folded into the epilogue (ConvArgs::gx1 ... set)
-int launch_fwd_gnb(const ConvArgs& a, int dtype, int nc, hipStream_t s) {
-    if (uses_kpack(dtype, 3, 1, 0, a.Cin, a.Cout, 0)) return nc == 1 ? launch_kpack<1, true>(a, s) : launch_kpack<2, true>(a, s);
-    if (dtype == VDM_F32) return launch_fwd_nc<float, float, 3, 1, 0, true>(a, nc, s);
-    return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, true>(a, nc, s);
+int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    if (p.family == VDM_CONV_VARIANT_KPACK) return p.nc == 1 ? launch_kpack<1, true>(a, s) : launch_kpack<2, true>(a, s);
+    if (p.dtype == VDM_F32) return launch_fwd_nc<float, float, 3, 1, 0, true>(a, p, s);
+    return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, true>(a, p, s);
 }
 
 // forward 3x3x3 stride-1 conv of y = silu(gn(x)) with GroupNorm + SiLU applied to the staged image (ConvArgs::gstats ... set; bf16)
-int launch_fwd_gnp(const ConvArgs& a, int out_f32, int nc, hipStream_t s) {
-    if (out_f32) return launch_fwd_geo<bf16_t, float, 3, 1, 0, 1, false, true>(a, s);
-    return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, false, true>(a, nc, s);
+int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s) {
+    if (p.out_f32) return launch_fwd_geo<bf16_t, float, 3, 1, 0, 1, false, true>(a, p, s);
+    return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, false, true>(a, p, s);
 }
 
 }  // namespace vdm

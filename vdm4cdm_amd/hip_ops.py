@@ -169,18 +169,13 @@ class Conv:
         d = self.desc(1, 2, 2, 2, dtype)
         assert w_master.dtype == torch.float32 and w_master.is_contiguous()
         assert w_master.numel() == self.ksize ** 3 * self.cout * self.cin
-        if self.wf is None or self.wf.device != w_master.device or self._packed_dtype != dtype:
-            self.wf = torch.empty(L.vdm_conv_packed_bytes(d, PACK_FWD), dtype=torch.uint8, device=w_master.device)
-            self.wd = None
-            self._packed_dtype = dtype
+        self.alloc_packed(w_master.device, dtype, need_dgrad)
         check(L.vdm_conv_pack_weights(d, PACK_FWD, _p(w_master), _p(self.wf), _s()), "vdm_conv_pack_weights(fwd)")
         if need_dgrad:
-            if self.wd is None:
-                self.wd = torch.empty(L.vdm_conv_packed_bytes(d, PACK_DGRAD), dtype=torch.uint8, device=w_master.device)
             check(L.vdm_conv_pack_weights(d, PACK_DGRAD, _p(w_master), _p(self.wd), _s()), "vdm_conv_pack_weights(dgrad)")
 
     def alloc_packed(self, device, dtype, need_dgrad):
-        """Make sure the packed-weight buffers exist (pack_many fills them)."""
+        """Make sure the packed-weight buffers exist (pack / pack_many fill them)."""
         L = _lib.lib()
         d = self.desc(1, 2, 2, 2, dtype)
         if self.wf is None or self.wf.device != device or self._packed_dtype != dtype:
@@ -189,6 +184,21 @@ class Conv:
             self._packed_dtype = dtype
         if need_dgrad and self.wd is None:
             self.wd = torch.empty(L.vdm_conv_packed_bytes(d, PACK_DGRAD), dtype=torch.uint8, device=device)
+
+    def _kernel_key(self, d, dgrad, dtype):
+        """Profiler key of the kernel family that runs this conv in one direction (one vdm_conv_kernel_variant call; a rolling-z or
+        eight-wave launch keeps the plain conv_fwd_kernel key)."""
+        var = _lib.lib().vdm_conv_kernel_variant(d, dgrad)
+        t, nc = _tname(dtype), _nc_for(self.cin if dgrad else self.cout, dtype)
+        if var == 1:
+            return f"conv_cls_kernel<{t},NC{nc},{'B' if dgrad and self.upsample else 'F'}>"
+        if var == 2:
+            return "conv_kpack_kernel"
+        if var == 3:
+            return f"conv_fwd_kernel<{t},k3,s1,NC2,split>"
+        if var == 4:
+            return f"conv_ksplit_kernel<{t},NC4>"
+        return f"conv_fwd_kernel<{t},k{self.ksize},s{1 if dgrad else self.stride},NC{nc}>"
 
     def out_shape(self, x):
         n, d, h, w, _ = x.shape
@@ -241,18 +251,8 @@ class Conv:
         if ev is not None:
             nvox = shp[0] * shp[1] * shp[2] * shp[3]
             es = x.element_size()
-            if self.ksize == 3 and self.upsample:
-                key = f"conv_cls_kernel<{_tname(x.dtype)},NC{_nc_for(self.cout, x.dtype)},F>"
-            elif L.vdm_conv_kernel_variant(d, 0) == 2:
-                key = "conv_kpack_kernel"
-            elif L.vdm_conv_kernel_variant(d, 0) == 3:
-                key = f"conv_fwd_kernel<{_tname(x.dtype)},k3,s1,NC2,split>"
-            elif L.vdm_conv_kernel_variant(d, 0) == 4:
-                key = f"conv_ksplit_kernel<{_tname(x.dtype)},NC4>"
-            else:
-                key = f"conv_fwd_kernel<{_tname(x.dtype)},k{self.ksize},s{self.stride},NC{_nc_for(self.cout, x.dtype)}>"
             alg = 2.0 * nvox * self.ksize ** 3 * self.cin * self.cout
-            _pe(ev, key, alg,
+            _pe(ev, self._kernel_key(d, 0, x.dtype), alg,
                 x.numel() * es + out.numel() * out.element_size() + (residual.numel() * es if residual is not None else 0),
                 alg * (8.0 / 27.0) if (self.ksize == 3 and self.upsample) else None)          # 8 merged taps per parity class
         return out
@@ -280,23 +280,14 @@ class Conv:
         if ev is not None:
             nvox = n * od * oh * ow
             es = dout.element_size()
-            if self.ksize == 3 and (self.stride == 2 or self.upsample):
-                key = f"conv_cls_kernel<{_tname(dout.dtype)},NC{_nc_for(self.cin, dout.dtype)},{'B' if self.upsample else 'F'}>"
-            elif L.vdm_conv_kernel_variant(d, 1) == 2:
-                key = "conv_kpack_kernel"
-            elif L.vdm_conv_kernel_variant(d, 1) == 3:
-                key = f"conv_fwd_kernel<{_tname(dout.dtype)},k3,s1,NC2,split>"
-            elif L.vdm_conv_kernel_variant(d, 1) == 4:
-                key = f"conv_ksplit_kernel<{_tname(dout.dtype)},NC4>"
-            else:
-                key = f"conv_fwd_kernel<{_tname(dout.dtype)},k{self.ksize},s1,NC{_nc_for(self.cin, dout.dtype)}>"
             alg = 2.0 * nvox * self.ksize ** 3 * self.cin * self.cout
             xf = None
             if self.ksize == 3 and self.upsample:
                 xf = alg * (8.0 / 27.0)                       # 8 classes x 8 merged taps on the coarse grid (= 64/216 of 27 fine taps)
             elif self.ksize == 3 and self.stride == 2:
                 xf = alg                                      # 27 taps in total over the 8 classes of the fine grid: nothing skipped
-            _pe(ev, key, alg, dout.numel() * es + out.numel() * es + (residual.numel() * es if residual is not None else 0), xf)
+            _pe(ev, self._kernel_key(d, 1, dout.dtype), alg,
+                dout.numel() * es + out.numel() * es + (residual.numel() * es if residual is not None else 0), xf)
         return out
 
     def gn_fold_ok(self, c1, c2, dtype):
@@ -329,11 +320,8 @@ class Conv:
         out.gnb_partials = part
         if ev is not None:
             es = dout.element_size()
-            var = L.vdm_conv_kernel_variant(d, 1)
-            key = "conv_kpack_kernel" if var == 2 else (f"conv_fwd_kernel<{_tname(dout.dtype)},k3,s1,NC2,split>" if var == 3 else
-                                                        (f"conv_ksplit_kernel<{_tname(dout.dtype)},NC4>" if var == 4 else
-                                                         f"conv_fwd_kernel<{_tname(dout.dtype)},k3,s1,NC{_nc_for(self.cin, dout.dtype)}>"))
-            _pe(ev, key + "+gnb", 2.0 * n * od * oh * ow * 27 * self.cin * self.cout, dout.numel() * es + 2 * out.numel() * es)
+            _pe(ev, self._kernel_key(d, 1, dout.dtype) + "+gnb", 2.0 * n * od * oh * ow * 27 * self.cin * self.cout,
+                dout.numel() * es + 2 * out.numel() * es)
         return out
 
     def dgw_ok(self, dout, c1, c2):
