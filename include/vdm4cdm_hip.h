@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 13
+#define VDM_ABI_VERSION 14
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -395,6 +395,49 @@ int vdm_ancestral_step_rows(float* z, const float* eps_hat, const float* eps_unc
 int vdm_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, const int32_t* seed_step, void* stream);
 /* *step_ptr += 1 (device-side step counter for the captured sampler graph). */
 int vdm_step_inc(int32_t* step_ptr, void* stream);
+
+/* ---- K11: DDNM range/null-space update (ABI v14; csrc/ddnm.hip) [REF src/utils.py:277-304] ------
+ * x_0t = (z - sigma_t*eps_hat)/alpha_t ; x_r = AT y + x_0t - AT A x_0t ; z <- w_z*z + w_x*x_r + scale*noise, fp32.
+ * Common contract: the scalars are read on the DEVICE.  e = *cursor is the index of the current network evaluation (monotonic over
+ * a whole DDNM run), sched[e][2] = {k, draw} names the row of coef[n_coef][8] = {1/alpha_t, sigma_t, w_z, w_x, scale, t_norm, 0, 0}
+ * and the number of this evaluation's noise draw, so one captured graph serves every evaluation (indices are clamped to the tables).
+ * noise == NULL: row r's noise is the Philox normal of (seeds[r], draw + 1, float4 group index within the row) - the field
+ * vdm_randn(seeds[r], stream_id = draw + 1) writes for one row, so a chain draws the same noise wherever it sits in a batch;
+ * batch_stream != 0: one stream over the whole batch, (seeds[0], draw + 1, float4 group index within the batch).
+ * eps_uncond != NULL: the w_cfg blend of vdm_ancestral_step_cfg.  x_r == NULL: the x_r write is skipped (only the last inner
+ * evaluation of an outer step is consumed).  Fields are [rows][per_row], per_row % 4 == 0, 16-byte aligned; operands with `*_rows`
+ * have 1 row (shared by the batch) or `rows`. */
+typedef struct vdm_ddnm_tables {
+    const float* coef;         /* DEVICE [n_coef][8] */
+    const int32_t* sched;      /* DEVICE [n_sched][2] = {k, draw} */
+    const int32_t* cursor;     /* DEVICE evaluation index */
+    int32_t n_coef, n_sched;
+    const uint64_t* seeds;     /* DEVICE [rows] (may be NULL when every launch gets a noise field) */
+    int32_t batch_stream, reserved;
+} vdm_ddnm_tables;
+/* Generic operator, first half: x0 = x_0t over n elements; the caller runs AT(A(x0)) and then vdm_ddnm_update. */
+int vdm_ddnm_x0(const float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const vdm_ddnm_tables* tables, float* x0,
+                int64_t n, void* stream);
+/* Generic operator, second half: x_r = (aty + x0) - atax0, then the z update. */
+int vdm_ddnm_update(float* z, const float* x0, const float* atax0, const float* aty, int aty_rows, const float* noise,
+                    const vdm_ddnm_tables* tables, float* x_r, int rows, int64_t per_row, void* stream);
+/* A = AT = mask: x_0t, x_r = (mask*y + x_0t) - mask*(mask*x_0t), the z update and the noise in ONE pass (reads z, eps_hat, mask, y;
+ * writes z, x_r) - bit for bit the generic pair around the callables x -> mask * x. */
+int vdm_ddnm_mask_step(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const float* mask, int mask_rows,
+                       const float* y, int y_rows, const float* noise, const vdm_ddnm_tables* tables, float* x_r, int rows,
+                       int64_t per_row, void* stream);
+/* A = mean over fz x fy x fx blocks of the [d][h][w] cube (factors in {1, 2, 4, 8} that divide it; w % 4 == 0), AT = nearest
+ * up-sampling: y is [y_rows][d/fz][h/fy][w/fx]; x_r = (y_block + x_0t) - mean_block(x_0t) and the z update in one launch (the block's
+ * rows are read twice by the same thread, the second time from cache). */
+int vdm_ddnm_blockmean_step(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const float* y, int y_rows, int d, int h,
+                            int w, int fz, int fy, int fx, const float* noise, const vdm_ddnm_tables* tables, float* x_r, int rows,
+                            void* stream);
+/* Travel back: z <- a*z + b*noise with {a, b} = travel[outer][2] (DEVICE table), noise supplied or Philox draw number `draw` keyed as
+ * above (only seeds / batch_stream of `tables` are used). */
+int vdm_ddnm_travel(float* z, const float* noise, const vdm_ddnm_tables* tables, const float* travel, int outer, int64_t draw, int rows,
+                    int64_t per_row, void* stream);
+/* *cursor += 1 ; *k_ptr = sched[*cursor][0] - the row index vdm_cond_table_step reads for the next evaluation. */
+int vdm_ddnm_advance(int32_t* cursor, const int32_t* sched, int n_sched, int32_t* k_ptr, void* stream);
 
 /* ---- K10: global gradient norm [REF trainVDM3D128_c_c_from_field_name_thick_lowbatch.py:45] -- */
 /* out[0] += sum x^2 (caller zeroes).  workspace: >= 2048 floats (fixed-order fold: bit-reproducible). */

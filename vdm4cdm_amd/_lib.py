@@ -63,10 +63,17 @@ class AugmentSample(C.Structure):
     _fields_ = [("sim", C.c_int32), ("anchor", C.c_int32 * 3), ("flip", C.c_int32 * 3), ("perm", C.c_int32 * 3)]
 
 
+class DdnmTables(C.Structure):
+    """vdm_ddnm_tables"""
+    _fields_ = [("coef", C.c_void_p), ("sched", C.c_void_p), ("cursor", C.c_void_p), ("n_coef", C.c_int32), ("n_sched", C.c_int32),
+                ("seeds", C.c_void_p), ("batch_stream", C.c_int32), ("reserved", C.c_int32)]
+
+
 PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
-ABI_VERSION = 13                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+_T = C.POINTER(DdnmTables)
+ABI_VERSION = 14                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -124,6 +131,12 @@ SIGNATURES = {
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_rows": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i64, _p]),
+    "vdm_ddnm_x0": (_i, [_p, _p, _p, _f, _T, _p, _i64, _p]),
+    "vdm_ddnm_update": (_i, [_p, _p, _p, _p, _i, _p, _T, _p, _i, _i64, _p]),
+    "vdm_ddnm_mask_step": (_i, [_p, _p, _p, _f, _p, _i, _p, _i, _p, _T, _p, _i, _i64, _p]),
+    "vdm_ddnm_blockmean_step": (_i, [_p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _i, _i, _p, _T, _p, _i, _p]),
+    "vdm_ddnm_travel": (_i, [_p, _p, _T, _p, _i, _i64, _i, _i64, _p]),
+    "vdm_ddnm_advance": (_i, [_p, _p, _i, _p, _p]),
     "vdm_randn": (_i, [_p, _i64, _u64, _u64, _p, _p]),
     "vdm_step_inc": (_i, [_p, _p]),
     "vdm_sumsq": (_i, [_p, _i64, _p, _p, _p]),

@@ -179,6 +179,34 @@ __host__ __device__ inline float u32_to_unit(uint32_t u) {          // (0,1]
     return ((float)(u >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 
+// ---- normals from Philox counters (the sampler's noise, the training step's eps) ----------------------
+__device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& n0, float& n1) {
+    const float r = sqrtf(-2.0f * __logf(u32_to_unit(u0)));
+    const float th = 6.28318530717958647692f * u32_to_unit(u1);
+    float s, c;
+    __sincosf(th, &s, &c);
+    n0 = r * c;
+    n1 = r * s;
+}
+
+// 4 normals for element group idx4 of stream (seed, sid)
+__device__ __forceinline__ float4 randn4(uint64_t seed, uint64_t sid, uint64_t idx4) {
+    uint32_t r[4];
+    Philox::gen((uint32_t)idx4, (uint32_t)(idx4 >> 32), (uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    float4 o;
+    box_muller(r[0], r[1], o.x, o.y);
+    box_muller(r[2], r[3], o.z, o.w);
+    return o;
+}
+
+// A product rounded on its own: the empty asm hides it from -ffp-contract=fast, which would otherwise fuse it into the add that consumes
+// it wherever the vectoriser happens not to pack the two products (no instruction is emitted).
+__device__ __forceinline__ float uncontracted_mul(float a, float b) {
+    float p = a * b;
+    asm("" : "+v"(p));
+    return p;
+}
+
 // ---- host-side error plumbing ------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);

@@ -592,25 +592,6 @@ __global__ void __launch_bounds__(256) fold_partials_kernel(const float* __restr
     if (threadIdx.x == 0) out[i] = accumulate ? out[i] + sm[0] : sm[0];
 }
 
-__device__ __forceinline__ void box_muller(uint32_t u0, uint32_t u1, float& n0, float& n1) {
-    const float r = sqrtf(-2.0f * __logf(u32_to_unit(u0)));
-    const float th = 6.28318530717958647692f * u32_to_unit(u1);
-    float s, c;
-    __sincosf(th, &s, &c);
-    n0 = r * c;
-    n1 = r * s;
-}
-
-// 4 normals for element group idx4 of stream (seed, sid)
-__device__ __forceinline__ float4 randn4(uint64_t seed, uint64_t sid, uint64_t idx4) {
-    uint32_t r[4];
-    Philox::gen((uint32_t)idx4, (uint32_t)(idx4 >> 32), (uint32_t)sid, (uint32_t)(sid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    float4 o;
-    box_muller(r[0], r[1], o.x, o.y);
-    box_muller(r[2], r[3], o.z, o.w);
-    return o;
-}
-
 __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed0, uint64_t sid, const int32_t* __restrict__ seed_step) {
     const uint64_t seed = mix_seed(seed0, seed_step);
     const int64_t n4 = (n + 3) >> 2;
@@ -746,14 +727,6 @@ __global__ void __launch_bounds__(256) schedule_grad_sums_kernel(const float* __
         part[(size_t)blockIdx.x * 2 + 0] = acc[0];
         part[(size_t)blockIdx.x * 2 + 1] = acc[1];
     }
-}
-
-// A product rounded on its own: the empty asm hides it from -ffp-contract=fast, which would otherwise fuse it into the add that consumes
-// it wherever the vectoriser happens not to pack the two products (no instruction is emitted).
-__device__ __forceinline__ float uncontracted_mul(float a, float b) {
-    float p = a * b;
-    asm("" : "+v"(p));
-    return p;
 }
 
 // One element of the ancestral update z <- ratio * (z - cs * e) + scale * noise, shared by ancestral_kernel and ancestral_rows_kernel.

@@ -829,6 +829,93 @@ def ancestral_step_rows(z, eps_hat, coef, step_ptr, seeds_dev, eps_uncond=None, 
                                     z.numel() // rows, _s()), "vdm_ancestral_step_rows")
 
 
+class DdnmTables:
+    """The device tables behind the DDNM kernels (vdm_ddnm_tables): coef [n, 8] fp32 = {1/alpha_t, sigma_t, w_z, w_x, scale, t_norm, 0, 0},
+    sched [n_sched, 2] int32 = {grid index k, draw number} per network evaluation, cursor int32 [1] (the evaluation index), k_ptr int32
+    [1] (the k of the current evaluation: what cond_table_step reads), seeds int64 [rows] or None (every launch gets a noise field);
+    batch_stream: one Philox stream over the whole batch from seeds[0] instead of one per row."""
+
+    def __init__(self, coef, sched, seeds=None, batch_stream=False):
+        dev = coef.device
+        assert coef.dtype == torch.float32 and coef.dim() == 2 and coef.shape[1] == 8 and sched.dtype == torch.int32 and sched.shape[1] == 2
+        assert seeds is None or (seeds.dtype == torch.int64 and seeds.device == dev)
+        _contig(coef, sched, seeds)
+        self.coef, self.sched, self.seeds = coef, sched, seeds
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.k_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.c = _lib.DdnmTables(coef=coef.data_ptr(), sched=sched.data_ptr(), cursor=self.cursor.data_ptr(), n_coef=coef.shape[0],
+                                 n_sched=sched.shape[0], seeds=None if seeds is None else seeds.data_ptr(),
+                                 batch_stream=int(bool(batch_stream)), reserved=0)
+        self.reset()
+
+    def reset(self, e=0):
+        """Cursor to evaluation e (device-side copies: no host synchronisation)."""
+        self.cursor.fill_(e)
+        self.k_ptr.copy_(self.sched[e, :1])
+
+    def advance(self):
+        check(_lib.lib().vdm_ddnm_advance(_p(self.cursor), _p(self.sched), self.sched.shape[0], _p(self.k_ptr), _s()), "vdm_ddnm_advance")
+
+    def _ref(self):
+        _p(self.coef), _p(self.sched), _p(self.cursor), _p(self.seeds)       # (side-stream bookkeeping of _p)
+        return C.byref(self.c)
+
+
+def _ddnm_rows(z, *same):
+    rows = z.shape[0]
+    assert z.dtype == torch.float32
+    for t in same:
+        assert t is None or (t.shape == z.shape and t.dtype == torch.float32), "DDNM fields must be fp32 tensors of z's shape"
+    return rows, z.numel() // rows
+
+
+def ddnm_x0(z, eps_hat, tables, out, eps_uncond=None, w_cfg=0.0):
+    """x_0t = (z - sigma_t eps_hat) / alpha_t at the cursor's grid index; eps_uncond: the w_cfg blend of K9."""
+    _contig(z, eps_hat, eps_uncond, out)
+    _ddnm_rows(z, eps_hat, eps_uncond, out)
+    check(_lib.lib().vdm_ddnm_x0(_p(z), _p(eps_hat), _p(eps_uncond), float(w_cfg), tables._ref(), _p(out), z.numel(), _s()), "vdm_ddnm_x0")
+    return out
+
+
+def ddnm_update(z, x0, atax0, aty, tables, noise=None, x_r=None):
+    """x_r = (aty + x0) - atax0 ; z <- w_z z + w_x x_r + scale noise (in place).  aty: z's shape or one row.  x_r None: not written."""
+    _contig(z, x0, atax0, aty, noise, x_r)
+    rows, per = _ddnm_rows(z, x0, atax0, noise, x_r)
+    assert aty.dtype == torch.float32 and aty.numel() in (per, rows * per)
+    check(_lib.lib().vdm_ddnm_update(_p(z), _p(x0), _p(atax0), _p(aty), aty.numel() // per, _p(noise), tables._ref(), _p(x_r), rows, per,
+                                     _s()), "vdm_ddnm_update")
+
+
+def ddnm_mask_step(z, eps_hat, mask, y, tables, noise=None, x_r=None, eps_uncond=None, w_cfg=0.0):
+    """The whole DDNM evaluation tail for A = AT = mask in one launch.  mask / y: z's shape or one row of it."""
+    _contig(z, eps_hat, eps_uncond, mask, y, noise, x_r)
+    rows, per = _ddnm_rows(z, eps_hat, eps_uncond, noise, x_r)
+    assert mask.dtype == y.dtype == torch.float32 and mask.numel() in (per, rows * per) and y.numel() in (per, rows * per)
+    check(_lib.lib().vdm_ddnm_mask_step(_p(z), _p(eps_hat), _p(eps_uncond), float(w_cfg), _p(mask), mask.numel() // per, _p(y),
+                                        y.numel() // per, _p(noise), tables._ref(), _p(x_r), rows, per, _s()), "vdm_ddnm_mask_step")
+
+
+def ddnm_blockmean_step(z, eps_hat, y, factors, tables, noise=None, x_r=None, eps_uncond=None, w_cfg=0.0):
+    """The whole DDNM evaluation tail for A = mean over factors = (fz, fy, fx) blocks, AT = nearest up-sampling, in one launch.
+    z is [rows, C, D, H, W] (the channels fold into the z axis); y is [rows or 1, C, D/fz, H/fy, W/fx]."""
+    _contig(z, eps_hat, eps_uncond, y, noise, x_r)
+    rows, per = _ddnm_rows(z, eps_hat, eps_uncond, noise, x_r)
+    fz, fy, fx = (int(f) for f in factors)
+    d, h, w = z.shape[-3] * (per // (z.shape[-3] * z.shape[-2] * z.shape[-1])), z.shape[-2], z.shape[-1]
+    nblk = fz * fy * fx
+    assert y.dtype == torch.float32 and y.numel() * nblk in (per, rows * per), "y must hold one value per block"
+    check(_lib.lib().vdm_ddnm_blockmean_step(_p(z), _p(eps_hat), _p(eps_uncond), float(w_cfg), _p(y), y.numel() * nblk // per, d, h, w, fz,
+                                             fy, fx, _p(noise), tables._ref(), _p(x_r), rows, _s()), "vdm_ddnm_blockmean_step")
+
+
+def ddnm_travel(z, tables, travel, outer, draw, noise=None):
+    """z <- a z + b noise with {a, b} = travel[outer] (device table [n, 2]); Philox draw number `draw`, or the supplied field."""
+    _contig(z, noise, travel)
+    rows, per = _ddnm_rows(z, noise)
+    assert travel.dtype == torch.float32 and 0 <= outer < travel.shape[0]
+    check(_lib.lib().vdm_ddnm_travel(_p(z), _p(noise), tables._ref(), _p(travel), int(outer), int(draw), rows, per, _s()), "vdm_ddnm_travel")
+
+
 def randn(out, seed, stream_id=0):
     L = _lib.lib()
     _contig(out)

@@ -120,8 +120,88 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
     return vdm
 
 
-def get_ddnm_result(vdm, y, A, AT, n_sampling_steps=250, l=10, return_all=False, verbose=0, **kwargs):
-    """DDNM range/null-space sampler with time travel (length l), on this package's VDM."""
+class MaskOperator:
+    """DDNM measurement y = mask * x (inpainting): A = AT = x -> mask * x.  `mask` broadcasts to the cube batch (B, *shape).  .A / .AT
+    are plain torch callables (any device); on the HIP backend get_ddnm_result(operator=) runs the fused mask kernel instead."""
+    kind = "mask"
+
+    def __init__(self, mask):
+        self.mask = torch.as_tensor(mask, dtype=torch.float32)
+        self._dev = {}
+
+    def _m(self, x):
+        m = self._dev.get(x.device)
+        if m is None:
+            m = self._dev[x.device] = self.mask.to(x.device)
+        return m
+
+    def A(self, x):
+        return x * self._m(x)
+
+    AT = A
+
+    def check(self, shape):
+        try:
+            ok = tuple(torch.broadcast_shapes(tuple(self.mask.shape), tuple(shape))) == tuple(shape)
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"MaskOperator: a mask of shape {tuple(self.mask.shape)} does not broadcast to the cube batch {tuple(shape)}")
+
+
+class BlockMeanOperator:
+    """DDNM measurement y = block-mean(x) (super-resolution): A = mean over fz x fy x fx blocks of the last three axes, AT = nearest
+    up-sampling, its pseudo-inverse (A AT = I, exactly: the block sum is a pairwise tree, so equal values add without rounding).
+    Each factor is 1, 2, 4 or 8.  On the HIP backend get_ddnm_result(operator=) runs the fused block-mean kernel instead."""
+    kind = "blockmean"
+
+    def __init__(self, factors):
+        factors = tuple(int(f) for f in factors)
+        if len(factors) != 3 or any(f not in (1, 2, 4, 8) for f in factors):
+            raise ValueError(f"BlockMeanOperator: factors = {factors} (three values out of 1, 2, 4, 8)")
+        self.factors = factors
+
+    def A(self, x):
+        n = 1
+        for ax, f in zip((-3, -2, -1), self.factors):
+            n *= f
+            while f > 1:
+                even = [slice(None)] * x.dim()
+                odd = [slice(None)] * x.dim()
+                even[ax], odd[ax] = slice(0, None, 2), slice(1, None, 2)
+                x = x[tuple(even)] + x[tuple(odd)]
+                f //= 2
+        return x * (1.0 / n) if n > 1 else x
+
+    def AT(self, y):
+        for ax, f in zip((-3, -2, -1), self.factors):
+            if f > 1:
+                y = y.repeat_interleave(f, dim=ax)
+        return y
+
+    def check(self, shape):
+        if len(shape) < 4 or any(d % f for d, f in zip(shape[-3:], self.factors)):
+            raise ValueError(f"BlockMeanOperator: factors {self.factors} do not divide the cube {tuple(shape[-3:])}")
+
+
+def get_ddnm_result(vdm, y, A=None, AT=None, n_sampling_steps=250, l=10, return_all=False, verbose=0, *, seed=None, seeds=None,
+                    noises=None, operator=None, use_graph=True, stats=None, **kwargs):
+    """DDNM range/null-space sampler with time travel (length l), on this package's VDM.
+    Without seed / seeds / noises / operator: the reference's loop as it stands (global torch RNG, eager evaluations).
+    With any of them: the seed- or noise-keyed sampler (vdm_model.ddnm_sample) - on the HIP backend one replayed hipGraph per network
+    evaluation with the DDNM update as HIP kernels.  seeds: one int per row of y, every row a chain of its own (its result does not
+    depend on the batch it sits in); seed: one stream for the whole batch; noises: every field in call order, z_1 first;
+    operator: a MaskOperator / BlockMeanOperator (A and AT may then be omitted; the update is one fused kernel); generic A / AT
+    run inside the captured step and must be device-only torch ops with fixed shapes (use_graph=False: the same kernels, un-captured).
+    The batch is y's row count (one seed per row of y).  stats: a dict that the device loop of the HIP backend fills for tests and
+    tools ({"graph", "evaluations", "allocated_before", "allocated_after"}: whether a captured step was replayed, the number of
+    network evaluations, torch.cuda.memory_allocated before the first and after the last evaluation); nothing is recorded without it."""
+    if seed is not None or seeds is not None or noises is not None or operator is not None:
+        from .vdm_model import ddnm_sample
+        return ddnm_sample(vdm.model, y, A, AT, operator, n_sampling_steps, l, return_all, verbose, seed, seeds, noises, use_graph,
+                           vdm.device, kwargs, stats)
+    if A is None or AT is None:
+        raise ValueError("get_ddnm_result: give A and AT, or operator=")
     if isinstance(l, int):
         l = np.full(n_sampling_steps, l)
     l = np.asarray(l)

@@ -360,22 +360,47 @@ class VDM(nn.Module):
         x_0t = (zt - sigma_t * pred_noise) / alpha_t
         return (alpha_s / alpha_t) * (1.0 - c), alpha_s * c, x_0t, sigma_s * torch.sqrt(c)
 
-    def sample_zt_given_zs(self, zs, t, s):
+    def sample_zt_given_zs(self, zs, t, s, noise=None):
+        """Forward diffusion s -> t (/root/reference/src/utils.py:294); `noise`: the field to use instead of a randn_like draw."""
         t, s = self._as_t(t, zs), self._as_t(s, zs)
         gamma_t, gamma_s = self.gamma(t), self.gamma(s)
         alpha_ts = self.alpha(gamma_t) / self.alpha(gamma_s)
         var = torch.sigmoid(gamma_t) - alpha_ts ** 2 * torch.sigmoid(gamma_s)
-        return alpha_ts * zs + torch.sqrt(var) * torch.randn_like(zs)
+        return alpha_ts * zs + torch.sqrt(var) * (torch.randn_like(zs) if noise is None else noise)
+
+    def _gamma_grid(self, n_sampling_steps):
+        """gamma in host fp64 on the fp32 time grid ``linspace(1, 0, n+1)`` (/root/reference/src/utils.py:286), either schedule."""
+        steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1).double()
+        with torch.no_grad():
+            if self.noise_schedule == "learned_linear":
+                return (self.gamma_b.double().cpu() + self.gamma_w.abs().double().cpu() * steps)
+            return self.gamma_min + (self.gamma_max - self.gamma_min) * steps
+
+    def ddnm_tables(self, n_sampling_steps, travel_lengths=None):
+        """Host fp64 tables of the DDNM sampler, computed like step_table.  coef [n, 8]: row k (t = steps[k], s = steps[k+1]) =
+        {1/alpha_t, sigma_t, w_z = (alpha_s/alpha_t)(1-c), w_x = alpha_s c, scale = sigma_s sqrt(c), t_norm, 0, 0} - the DDNM form of
+        sample_zs_given_zt(return_ddnm=True).  With travel_lengths (L of every outer step) also travel [n, 2]: row i =
+        {alpha_t/alpha_s, sqrt(sigma_t^2 - (alpha_t/alpha_s)^2 sigma_s^2)} for t = steps[i-L], s = steps[i] (sample_zt_given_zs)."""
+        g = self._gamma_grid(n_sampling_steps)
+        g_t, g_s = g[:-1], g[1:]
+        c = -torch.expm1(g_s - g_t)
+        a_t, a_s = torch.sqrt(torch.sigmoid(-g_t)), torch.sqrt(torch.sigmoid(-g_s))
+        s_t, s_s = torch.sqrt(torch.sigmoid(g_t)), torch.sqrt(torch.sigmoid(g_s))
+        t_norm = (g_t - self.gamma_min) / (self.gamma_max - self.gamma_min)
+        zero = torch.zeros_like(c)
+        coef = torch.stack([1.0 / a_t, s_t, (a_s / a_t) * (1.0 - c), a_s * c, s_s * torch.sqrt(c), t_norm, zero, zero], dim=1)
+        if travel_lengths is None:
+            return coef
+        i = torch.arange(n_sampling_steps)
+        gt, gs = g[i - torch.as_tensor(list(travel_lengths), dtype=torch.int64)], g[i]
+        a_ts = torch.sqrt(torch.sigmoid(-gt)) / torch.sqrt(torch.sigmoid(-gs))
+        var = torch.sigmoid(gt) - a_ts ** 2 * torch.sigmoid(gs)
+        return coef, torch.stack([a_ts, torch.sqrt(var)], dim=1)
 
     def step_table(self, n_sampling_steps):
         """Host fp64 table [n, 4] = {alpha_s/alpha_t, c*sigma_t, sigma_s*sqrt(c), t_norm} on the fp32 time grid
         ``linspace(1, 0, n+1)`` (/root/reference/src/utils.py:286)."""
-        steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1).double()
-        with torch.no_grad():
-            if self.noise_schedule == "learned_linear":
-                g = (self.gamma_b.double().cpu() + self.gamma_w.abs().double().cpu() * steps)
-            else:
-                g = self.gamma_min + (self.gamma_max - self.gamma_min) * steps
+        g = self._gamma_grid(n_sampling_steps)
         g_t, g_s = g[:-1], g[1:]
         c = -torch.expm1(g_s - g_t)
         a_t, a_s = torch.sqrt(torch.sigmoid(-g_t)), torch.sqrt(torch.sigmoid(-g_s))
@@ -471,27 +496,10 @@ def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     else:
         seed = int(seed)
-    noise_buf = torch.empty_like(z) if noises is not None else None
-
-    # The conditioning of every step is known up front: ONE K6 launch embeds all n time values (one table row per step), one more
-    # the vector conditionings; inside the step a single gather-add kernel builds the table (device-side step counter).
-    W = net.table_width
-    table_t = table_v = None
+    feed = _NoiseFeed(noises, z) if noises is not None else None
+    noise_buf = feed.buf if feed is not None else None
     cfg = w_cfg is not None
-    with torch.no_grad():
-        fl = net.flat.detach()
-        if net.t_conditioning:
-            table_t = ops.CondTable(net.cond_specs(coef[:, 3].contiguous(), None, fl, which="t"), n, W).forward(save=False)
-        vs = [v.to(device=dev, dtype=torch.float32).expand(B, -1).contiguous() for v in v_conditionings]
-        if cfg:                                            # guided + v-masked rows of one batch-doubled forward (VDM._cfg_pair)
-            vs = [torch.cat([v, m], dim=0).contiguous() for v, m in zip(vs, mask_fn(vs))]
-        R = 2 * B if cfg else B                            # rows the UNet sees
-        if vs:
-            table_v = ops.CondTable(net.cond_specs(None, vs, fl, which="v"), R, W).forward(save=False)
-    if s_cond is not None:                                 # one conditioning cube serves every row of the batch
-        s_cond = s_cond.to(dev).expand(B, *s_cond.shape[1:])
-        s_cond = (torch.cat([s_cond, s_cond], dim=0) if cfg else s_cond).contiguous()
-    table = torch.zeros(R, W, device=dev)
+    table_t, table_v, table, s_cond, R, W = _sampler_conditioning(net, coef[:, 3].contiguous(), B, s_cond, v_conditionings, cfg, mask_fn)
     zz = torch.empty(R, *z.shape[1:], device=dev) if cfg else z
 
     def one_step():
@@ -512,34 +520,17 @@ def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_
 
     graph = None
     if use_graph and n > 2:
-        # warm-up on a side stream (packs weights, sizes the allocator), then capture one step
-        side = torch.cuda.Stream(device=dev)
         z_keep = z.clone()
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            if noise_buf is not None:
-                noise_buf.copy_(noises[0].to(z))
-            one_step()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        z.copy_(z_keep)
-        step.zero_()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            one_step()
-        z.copy_(z_keep)             # capture does not execute, but keep the state explicit
-        step.zero_()
+
+        def restore():
+            z.copy_(z_keep)
+            step.zero_()
+
+        graph = _capture_step(one_step, dev, restore, prime=None if feed is None else lambda: noise_buf.copy_(noises[0].to(z)))
     zs = torch.empty((n,) + tuple(z.shape), dtype=z.dtype, device=dev) if return_all else None
-    # supplied noise fields (tests / oracle comparisons; the product path draws them in-kernel): uploaded in blocks of <= 256 MB and copied
-    # device-to-device per step - one pageable host-to-device copy between every two graph replays was the only thing the tests that
-    # intermittently took the process down (round 4) did differently from the product's sampling loop
-    blk, dev_block = 1, None
-    if noise_buf is not None:
-        blk = max(1, min(n, (256 << 20) // max(1, z.numel() * z.element_size())))
     for i in range(n):
-        if noise_buf is not None:
-            if i % blk == 0:
-                dev_block = torch.stack([noises[k].to(dtype=z.dtype) for k in range(i, min(n, i + blk))]).to(dev)
-            noise_buf.copy_(dev_block[i % blk])
+        if feed is not None:
+            feed.load(i)
         if graph is not None:
             graph.replay()
         else:
@@ -549,6 +540,268 @@ def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_
         if verbose and (i % 50 == 0 or i == n - 1):
             print(f"sampling: {i + 1}/{n}", flush=True)
     return zs if return_all else z
+
+
+def _sampler_conditioning(net, t_norm, B, s_cond, v_conditionings, cfg, mask_fn):
+    """The conditioning of every step of a sampling loop is known up front: ONE K6 launch embeds all time values (one table row per
+    grid index), one more the vector conditionings; inside the step a single gather-add kernel (cond_table_step) builds the table from
+    a device-side row index.  cfg: guided + v-masked rows of one batch-doubled forward (VDM._cfg_pair).  Returns (table_t, table_v,
+    table [R, W], s_cond expanded to the R rows the UNet sees, R, W)."""
+    from . import hip_ops as ops
+    dev = net.flat.device
+    W = net.table_width
+    table_t = table_v = None
+    with torch.no_grad():
+        fl = net.flat.detach()
+        if net.t_conditioning:
+            table_t = ops.CondTable(net.cond_specs(t_norm, None, fl, which="t"), t_norm.shape[0], W).forward(save=False)
+        vs = [v.to(device=dev, dtype=torch.float32).expand(B, -1).contiguous() for v in v_conditionings]
+        if cfg:
+            vs = [torch.cat([v, m], dim=0).contiguous() for v, m in zip(vs, mask_fn(vs))]
+        R = 2 * B if cfg else B                            # rows the UNet sees
+        if vs:
+            table_v = ops.CondTable(net.cond_specs(None, vs, fl, which="v"), R, W).forward(save=False)
+    if s_cond is not None:                                 # one conditioning cube serves every row of the batch
+        s_cond = s_cond.to(dev).expand(B, *s_cond.shape[1:])
+        s_cond = (torch.cat([s_cond, s_cond], dim=0) if cfg else s_cond).contiguous()
+    return table_t, table_v, torch.zeros(R, W, device=dev), s_cond, R, W
+
+
+def _capture_step(one_step, dev, restore, prime=None):
+    """Warm-up of `one_step` on a side stream (packs weights, sizes the allocator; `prime` runs first on that stream), then its capture
+    in a hipGraph; `restore` puts the loop's state (z, device counters) back after each of the two."""
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        if prime is not None:
+            prime()
+        one_step()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    restore()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        one_step()
+    restore()                       # capture does not execute, but keep the state explicit
+    return graph
+
+
+class _NoiseFeed:
+    """Supplied noise fields (tests / oracle comparisons; the product path draws them in-kernel): uploaded in blocks of <= 256 MB and copied
+    device-to-device into `buf` per draw - one pageable host-to-device copy between every two graph replays was the only thing the tests
+    that intermittently took the process down (round 4) did differently from the product's sampling loop."""
+
+    def __init__(self, noises, like):
+        self.noises, self.like, self.n = noises, like, len(noises)
+        self.buf = torch.empty_like(like)
+        self.blk = max(1, min(self.n, (256 << 20) // max(1, like.numel() * like.element_size())))
+        self.first, self.block = None, None
+
+    def load(self, i):
+        first = i - i % self.blk
+        if first != self.first:
+            self.block = torch.stack([self.noises[k].to(dtype=self.like.dtype) for k in range(first, min(self.n, first + self.blk))]).to(
+                self.like.device)
+            self.first = first
+        self.buf.copy_(self.block[i - first])
+
+
+# ------------------------------------------------------------------------------------------------------------------ DDNM
+def ddnm_lengths(n_sampling_steps, l):
+    """The time-travel length of every outer step as an integer array (an int: the same for all)."""
+    import numpy as np
+    if isinstance(l, (int, np.integer)):
+        l = np.full(n_sampling_steps, int(l))
+    l = np.asarray(l)
+    if not (l.ndim == 1 and len(l) == n_sampling_steps and np.issubdtype(l.dtype, np.integer) and np.all(l >= 0)):
+        raise ValueError("l must be a non-negative integer or an integer array of length n_sampling_steps")
+    return l
+
+
+def ddnm_schedule(n_sampling_steps, l):
+    """The DDNM loop of /root/reference/src/utils.py:290-299 unrolled on the host.  Outer step i travels back L = min(l[i], i) grid
+    steps (one draw) and then evaluates the network at t = steps[k], s = steps[k+1] for k = i-L .. i (one draw each).  Returns
+    k / draw / outer: per evaluation, in order, the grid index, the number of its update draw and its outer step; L / travel_draw: per
+    outer step; n_draws (z_1 is not counted: draw d is the d+1-th field after it)."""
+    l = ddnm_lengths(n_sampling_steps, l)
+    out = {"k": [], "draw": [], "outer": [], "L": [], "travel_draw": []}
+    d = 0
+    for i in range(n_sampling_steps):
+        L = int(min(l[i], i))
+        out["L"].append(L)
+        out["travel_draw"].append(d)
+        d += 1
+        for j in range(L, -1, -1):
+            out["k"].append(i - j)
+            out["draw"].append(d)
+            out["outer"].append(i)
+            d += 1
+    out["n_draws"] = d
+    return out
+
+
+def ddnm_sample(model, y, A, AT, operator, n, l, return_all, verbose, seed, seeds, noises, use_graph, device, kwargs, stats=None):
+    """The seed- / noise-keyed DDNM sampler behind utils.get_ddnm_result's new keywords: on the HIP backend the device loop
+    hip_ddnm_sampler, on the torch backend the reference-order loop with the same arguments (noises in call order; seeds: one
+    generator per chain, manual_seed(s + 1), as VDM.sample's torch path; seed: one generator for the batch).  The batch is y's row
+    count.  stats: see utils.get_ddnm_result."""
+    B = y.shape[0]
+    cube = tuple(model.score_model.shape)
+    sch = ddnm_schedule(n, l)
+    if seeds is not None:
+        seeds = [int(s) for s in seeds]
+        if len(seeds) != B:
+            raise ValueError(f"get_ddnm_result: {len(seeds)} seeds for {B} rows of y (one seed per chain)")
+    if sum(a is not None for a in (seed, seeds, noises)) > 1:
+        raise ValueError("get_ddnm_result: seed=, seeds= and noises= cannot be combined")
+    if noises is not None and len(noises) != 1 + sch["n_draws"]:
+        raise ValueError(f"get_ddnm_result: {len(noises)} noises, the schedule draws {1 + sch['n_draws']} fields (z_1 first)")
+    if operator is not None:
+        operator.check((B,) + cube)
+        A, AT = operator.A, operator.AT
+    if A is None or AT is None:
+        raise ValueError("get_ddnm_result: give A and AT, or operator=")
+    if noises is not None:
+        z = noises[0].clone()
+    elif seeds is not None:
+        z = torch.cat([torch.randn((1,) + cube, generator=torch.Generator().manual_seed(s)) for s in seeds])
+    elif seed is not None:
+        z = torch.randn((B,) + cube, generator=torch.Generator().manual_seed(int(seed)))
+    else:
+        z = torch.randn((B,) + cube, device=device)
+    z = z.to(device=device, dtype=torch.float32).contiguous()
+    y = y.to(device)
+    with torch.no_grad():
+        if model._hip(z):
+            return hip_ddnm_sampler(model, z, y, A, AT, operator, n, sch, noises, seed, seeds, use_graph, return_all, verbose, kwargs,
+                                    stats)
+        gens = None
+        if seeds is not None:
+            gens = [torch.Generator().manual_seed(s + 1) for s in seeds]
+        elif seed is not None:
+            gens = torch.Generator().manual_seed(int(seed) + 1)
+
+        def draw(d):
+            if noises is not None:
+                return noises[d + 1].to(z)
+            if isinstance(gens, list):
+                return torch.cat([torch.randn((1,) + cube, generator=g) for g in gens]).to(z)
+            return torch.randn_like(z) if gens is None else torch.randn(z.shape, generator=gens).to(z)
+
+        steps = torch.linspace(1.0, 0.0, n + 1, device=device)
+        ATy = AT(y)
+        xs, x_r, e = [], None, 0
+        for i in range(n):
+            L = sch["L"][i]
+            z = model.sample_zt_given_zs(zs=z, t=steps[i - L], s=steps[i], noise=draw(sch["travel_draw"][i]))
+            for _ in range(L + 1):
+                k = sch["k"][e]
+                w_z, w_x, x0, scale = model.sample_zs_given_zt(zt=z, t=steps[k], s=steps[k + 1], return_ddnm=True, **kwargs)
+                x_r = ATy + x0 - AT(A(x0))
+                z = w_z * z + w_x * x_r + scale * draw(sch["draw"][e])
+                e += 1
+            if return_all:
+                xs.append(x_r)
+        return torch.stack(xs, dim=0) if return_all else x_r
+
+
+def hip_ddnm_sampler(model, z, y, A, AT, operator, n, sch, noises, seed, seeds, use_graph, return_all, verbose, kwargs, stats=None):
+    """DDNM on the HIP backend.  The captured inner step is [conditioning-table gather at k, UNet forward, DDNM kernels (+ the callables
+    AT(A(.)) of a generic operator), cursor advance]; the host loop launches the travel-back kernel and replays the step L+1 times per
+    outer step - no host synchronisation, no allocation after the capture.  All scalars come from device tables at the device cursor
+    (ops.DdnmTables); noise is supplied (`noises`, z_1 first) or drawn in the kernels, keyed by (seeds[r], draw + 1) per row, or by
+    (seed, draw + 1) over the whole batch.  A generic operator must be device-only torch ops with fixed shapes to be captured
+    (use_graph=False runs the same kernels un-captured)."""
+    from . import hip_ops as ops
+    from .unet_hip import hip_unet_apply
+    net, dev, B = model.score_model, z.device, z.shape[0]
+    coef, travel = model.ddnm_tables(n, sch["L"])
+    coef = coef.to(device=dev, dtype=torch.float32).contiguous()
+    travel = travel.to(device=dev, dtype=torch.float32).contiguous()
+    E = len(sch["k"])
+    # (one pad row: the advance after the last evaluation reads it)
+    sched = torch.tensor(list(zip(sch["k"] + sch["k"][-1:], sch["draw"] + sch["draw"][-1:])), dtype=torch.int32).to(dev)
+    seeds_dev, feed = None, None
+    if noises is not None:
+        feed = _NoiseFeed(noises, z)
+    elif seeds is not None:
+        seeds_dev = torch.tensor(seeds, dtype=torch.int64).to(dev)
+    else:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        seeds_dev = torch.tensor([seed], dtype=torch.int64).to(dev)
+    tables = ops.DdnmTables(coef, sched, seeds_dev, batch_stream=noises is None and seeds is None)
+    noise_buf = feed.buf if feed is not None else None
+    cfg = model.w_cfg is not None and not model.training
+    w_cfg = float(model.w_cfg) if cfg else 0.0
+    if cfg:
+        assert "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+    table_t, table_v, table, s_cond, R, W = _sampler_conditioning(net, coef[:, 5].contiguous(), B, kwargs.get("s_conditioning"),
+                                                                  list(kwargs.get("v_conditionings") or []), cfg, model.cfg_mask)
+    zz = torch.empty(R, *z.shape[1:], device=dev) if cfg else z
+    x_r = torch.empty_like(z)
+    kind = getattr(operator, "kind", None)
+    y = y.to(torch.float32)
+    if kind == "mask":
+        m = operator.mask.to(device=dev, dtype=torch.float32)
+        rows = slice(0, 1) if (m.dim() < z.dim() or m.shape[0] == 1) else slice(None)
+        m_dev = torch.broadcast_to(m, z.shape)[rows].contiguous()
+        y_dev = torch.broadcast_to(y, z.shape).contiguous()
+    elif kind == "blockmean":
+        y_dev = y.contiguous()
+    else:
+        aty = torch.broadcast_to(AT(y).to(torch.float32), z.shape).contiguous()
+        x0 = torch.empty_like(z)
+
+    def one_step():
+        if table_t is not None or table_v is not None:
+            ops.cond_table_step(table_t, table_v, tables.k_ptr, R, W, table)
+        if cfg:
+            zz[:B].copy_(z)
+            zz[B:].copy_(z)
+        eps_hat = hip_unet_apply(net, zz, s_cond, table=table).contiguous()
+        eh, eu = (eps_hat[:B], eps_hat[B:]) if cfg else (eps_hat, None)
+        if kind == "mask":
+            ops.ddnm_mask_step(z, eh, m_dev, y_dev, tables, noise_buf, x_r, eu, w_cfg)
+        elif kind == "blockmean":
+            ops.ddnm_blockmean_step(z, eh, y_dev, operator.factors, tables, noise_buf, x_r, eu, w_cfg)
+        else:
+            ops.ddnm_x0(z, eh, tables, x0, eu, w_cfg)
+            ops.ddnm_update(z, x0, AT(A(x0)).contiguous(), aty, tables, noise_buf, x_r)
+        tables.advance()
+
+    graph = None
+    if use_graph and E > 2:
+        z_keep = z.clone()
+
+        def restore():
+            z.copy_(z_keep)
+            tables.reset()
+
+        graph = _capture_step(one_step, dev, restore, prime=None if feed is None else lambda: noise_buf.copy_(noises[1].to(z)))
+    xs = torch.empty((n,) + tuple(z.shape), dtype=z.dtype, device=dev) if return_all else None
+    if stats is not None:
+        stats.update(evaluations=E, graph=graph is not None, allocated_before=torch.cuda.memory_allocated(dev))
+    e = 0
+    for i in range(n):
+        L = sch["L"][i]
+        if L > 0:                                          # (L == 0: a = 1, b = 0 - the draw is numbered, nothing is launched)
+            if feed is not None:
+                feed.load(sch["travel_draw"][i] + 1)
+            ops.ddnm_travel(z, tables, travel, i, sch["travel_draw"][i], noise_buf)
+        for _ in range(L + 1):
+            if feed is not None:
+                feed.load(sch["draw"][e] + 1)
+            if graph is not None:
+                graph.replay()
+            else:
+                one_step()
+            e += 1
+        if xs is not None:
+            xs[i].copy_(x_r)
+        if verbose and (i % 25 == 0 or i == n - 1):
+            print(f"ddnm {i + 1}/{n}", flush=True)
+    if stats is not None:
+        stats["allocated_after"] = torch.cuda.memory_allocated(dev)
+    return xs if return_all else x_r
 
 
 _TRAIN_GENS = {}
