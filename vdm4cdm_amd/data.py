@@ -90,9 +90,9 @@ class SyntheticAstroDataModule:
             batch = {"conditioning": cond, "x": x, "conditioning_values": [params[:, :self.n_params]] if self.n_params else []}
         return batch
 
-    def _loader(self, base_seed, n_items, batch_size, rank=0, world=1):
+    def _loader(self, base_seed, n_items, batch_size, rank=0, world=1, start_batch=0):
         n_batches = max(1, n_items // (batch_size * world))
-        for b in range(n_batches):
+        for b in range(start_batch, n_batches):
             key = (base_seed, (b * world + rank) % self.pool, batch_size)
             if key not in self._cache:
                 self._cache[key] = self._make_batch(base_seed + key[1], batch_size)
@@ -106,8 +106,17 @@ class SyntheticAstroDataModule:
             return [a.to(self.device, non_blocking=True) for a in v]
         return v.to(self.device, non_blocking=True)
 
-    def train_dataloader(self, rank=0, world=1):
-        return self._loader(self.seed + 7919 * rank, self.n_train, self.batch_size, rank, world)
+    def train_dataloader(self, rank=0, world=1, start_batch=0):
+        """start_batch: begin at that batch of the epoch (a resumed run; the batches are a pure function of their index)."""
+        return self._loader(self.seed + 7919 * rank, self.n_train, self.batch_size, rank, world, start_batch)
+
+    def state_dict(self):
+        """What identifies the batch sequence (the position inside the epoch is the trainer's `batches_into_epoch`)."""
+        return {"kind": type(self).__name__, "seed": int(self.seed), "n_train": int(self.n_train), "batch_size": int(self.batch_size),
+                "cropsize": int(self.cropsize), "dim": int(self.dim), "pool": int(self.pool)}
+
+    def load_state_dict(self, state):
+        _check_same_module(self.state_dict(), state)
 
     def val_dataloader(self, rank=0, world=1):
         return self._loader(self.seed + 500000, self.n_val, self.batch_size, rank, world)
@@ -207,6 +216,7 @@ class AstroDataModule:
             self.train_idx, self.valid_idx = order[:n_train], order[n_train:]
         else:
             self.test_idx = list(range(self.nsamples))
+        self._epoch_gen_state = None                              # _gen's state where the current training epoch drew its order
         self._dev_fields = None
 
     # -- normalisation pair (CAMELS_3D_dataset.py:146-156) --------------------------------------------
@@ -289,10 +299,11 @@ class AstroDataModule:
         idx = (idx * (total // len(idx) + 1))[:total]
         return idx[rank::world]
 
-    def _loader(self, indices, train, shuffle, rank=0, world=1, kind="train"):
+    def _loader(self, indices, train, shuffle, rank=0, world=1, kind="train", start_batch=0):
         gen = self._aug_generator(kind, rank)                     # (seeded once per (kind, rank); never re-seeded)
         idx = list(indices)
         if shuffle:
+            self._epoch_gen_state = self._gen.get_state()
             idx = [idx[i] for i in torch.randperm(len(idx), generator=self._gen).tolist()]
         if kind == "eval" and world > 1:
             # validation / test: every item exactly once over the ranks (strided, NO wrap-around padding: a duplicated item would be
@@ -301,17 +312,48 @@ class AstroDataModule:
             idx = idx[rank::world]
         else:
             idx = self.shard(idx, rank, world)                   # data parallelism: equal-length strided shards of the epoch
-        for b0 in range(0, len(idx), self.batch_size):
+        # (start_batch > 0: the first batches of the epoch are skipped - no augmentation draw, no launch)
+        for b0 in range(start_batch * self.batch_size, len(idx), self.batch_size):
             yield self.make_batch([self.draw_sample(i, train, gen) for i in idx[b0:b0 + self.batch_size]])
 
-    def train_dataloader(self, rank=0, world=1):
-        return self._loader(self.train_idx, True, True, rank, world, "train")
+    def train_dataloader(self, rank=0, world=1, start_batch=0):
+        """start_batch: begin at that batch of the epoch (a resumed run, after load_state_dict: the epoch's order is re-drawn from the
+        saved epoch-start state of the shuffle generator, which ends up where the uninterrupted run's is)."""
+        return self._loader(self.train_idx, True, True, rank, world, "train", start_batch)
+
+    def state_dict(self):
+        """The shuffle generator's state at the start of the current training epoch (before the first epoch: its current state) and the
+        current state of every augmentation generator of this rank (train and eval; they draw lazily, batch by batch).  The position
+        inside the epoch is the trainer's `batches_into_epoch`."""
+        st = self._gen.get_state() if self._epoch_gen_state is None else self._epoch_gen_state
+        return {"kind": type(self).__name__, "seed": self._seed, "nsamples": int(self.nsamples), "batch_size": int(self.batch_size),
+                "crop": int(self.crop), "stage": self.stage, "epoch_gen_state": st.clone(),
+                "aug_generators": {f"{k}:{r}": g.get_state() for (k, r), g in self._aug_gens.items()}}
+
+    def load_state_dict(self, state):
+        _check_same_module(self.state_dict(), state, skip=("epoch_gen_state", "aug_generators"))
+        self._gen.set_state(state["epoch_gen_state"])
+        self._epoch_gen_state = state["epoch_gen_state"].clone()
+        for key, st in state["aug_generators"].items():
+            kind, rank = key.rsplit(":", 1)
+            self._aug_generator(kind, int(rank)).set_state(st)
 
     def val_dataloader(self, rank=0, world=1):
         return self._loader(self.valid_idx, True, False, rank, world, "eval")          # (the reference's valid split shares the "fit" transforms)
 
     def test_dataloader(self, rank=0, world=1):
         return self._loader(self.test_idx, False, False, rank, world, "eval")
+
+
+def _check_same_module(mine, saved, skip=()):
+    """ValueError unless the saved data-module state was written by a module configured like this one."""
+    if not isinstance(saved, dict) or saved.get("kind") != mine["kind"]:
+        raise ValueError(f"data-module state of a {saved.get('kind') if isinstance(saved, dict) else type(saved).__name__} cannot be loaded "
+                         f"into a {mine['kind']}")
+    bad = [f"{k}: saved {saved.get(k)!r}, this module {v!r}" for k, v in mine.items() if k not in skip and saved.get(k) != v]
+    if bad:
+        raise ValueError(f"the data-module state does not match this {mine['kind']} ({'; '.join(bad)}): a run resumes only on the data "
+                         "module configuration that it was started with")
 
 
 def _cv_keep(n):

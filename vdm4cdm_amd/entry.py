@@ -12,7 +12,8 @@
 * ``generate_3D.py <model_name> <save_path> <runtype>`` -> ``generate_3d(argv)`` (/root/reference/generate_3D.py).
 Environment knobs (build-side, all optional): VDM4CDM_MAX_STEPS, VDM4CDM_PRECISION (bf16|fp32), VDM4CDM_SAMPLING_STEPS,
 VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing config), VDM4CDM_SAMPLE_BATCH (chains per sampler
-call and rank in generate_3D*; default 1).
+call and rank in generate_3D*; default 1), VDM4CDM_RESUME (a checkpoint of the same run to continue from, or "last": the newest one
+in the run directory).
 Multi-GPU: launch the same script under ``python -m torch.distributed.run --nproc-per-node N`` (one rank per GPU, RCCL).
 """
 import argparse
@@ -40,6 +41,42 @@ def _seed_everything(seed=42):
     torch.manual_seed(seed)
     from .vdm_model import reset_train_generators
     reset_train_generators()                 # the training step's own generators restart from the new seed
+
+
+def _resume_path(log_dir, experiment_name):
+    """VDM4CDM_RESUME: the checkpoint a training script continues from (Trainer.fit(ckpt_path=)); unset: a fresh run.  "last" picks the
+    checkpoint of this run's directory with the highest `global_step` as read from the files (not by name or mtime).  Read before any
+    model or GPU work, so that a value that names no usable file fails at once."""
+    raw = os.environ.get("VDM4CDM_RESUME")
+    if raw is None:
+        return None
+    from .trainer import read_checkpoint
+
+    def head(path):
+        try:
+            ck = read_checkpoint(path, mmap=True)
+            return int(ck["global_step"]), "trainer_state" in ck
+        except Exception:
+            return None
+
+    if raw.strip() == "last":
+        import glob
+        d = os.path.join(log_dir, experiment_name, "checkpoints")
+        found = [(h[0], f) for f in sorted(glob.glob(os.path.join(d, "*.ckpt"))) for h in [head(f)] if h is not None]
+        if not found:
+            raise SystemExit(f"VDM4CDM_RESUME=last: no readable checkpoint in {d}")
+        path = max(found)[1]
+    else:
+        path = raw
+        if not os.path.isfile(path):
+            raise SystemExit(f"VDM4CDM_RESUME={raw!r}: no such file (give a checkpoint written by this run, or 'last')")
+    h = head(path)
+    if h is None:
+        raise SystemExit(f"VDM4CDM_RESUME={raw!r}: {path} is not a readable checkpoint")
+    if not h[1]:
+        raise SystemExit(f"VDM4CDM_RESUME={raw!r}: {path} is a weights-only checkpoint without trainer_state (optimizer, random streams, "
+                         "data position): a run cannot be resumed from it")
+    return path
 
 
 def _figure_closure(dm, thickness, with_values):
@@ -81,6 +118,8 @@ def train_vdm3d(variant, argv=None):
         raise SystemExit("usage: <script> <field_in> <field_out> <cropsize>")
     field_in, field_out, cropsize = argv[0], argv[1], int(argv[2])
     dataset_name, chs, n_values, val_every, name_pat, thick = VDM3D_VARIANTS[variant]
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
     batch_size = 2
 
@@ -99,10 +138,9 @@ def train_vdm3d(variant, argv=None):
                              learning_rate=3.0e-4)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=val_every,
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
-                      default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"),
-                      experiment_name=name_pat.format(i=field_in, o=field_out, c=cropsize),
+                      default_root_dir=log_dir, experiment_name=name,
                       n_val_sampling_steps=int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250)))
-    trainer.fit(model=vdm, datamodule=dm)
+    trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)
     return trainer
 
 
@@ -130,6 +168,8 @@ def train3d_c_c(variant, argv=None):
     field_in, field_out = argv
     cropsize, name_pat, thick = TRAIN3D_VARIANTS[variant]
     c = TRAIN3D_COMMON
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"), name_pat.format(i=field_in, o=field_out)
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
 
     def return_func(fields, params):
@@ -146,10 +186,9 @@ def train3d_c_c(variant, argv=None):
                              gamma_max=c["gamma_max"], noise_schedule=c["noise_schedule"], learning_rate=c["learning_rate"])
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=c["val_check_interval"],
                       gradient_clip_val=c["gradient_clip_val"], every_n_train_steps=c["every_n_train_steps"],
-                      default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"),
-                      experiment_name=name_pat.format(i=field_in, o=field_out),
+                      default_root_dir=log_dir, experiment_name=name,
                       n_val_sampling_steps=int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250)))
-    trainer.fit(model=vdm, datamodule=dm)
+    trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)
     return trainer
 
 
@@ -187,6 +226,8 @@ def train_sfm3d(variant, argv=None):
         raise SystemExit("usage: <script> <field_in> <field_out> <cropsize>")
     field_in, field_out, cropsize = argv[0], argv[1], int(argv[2])
     dataset_name, chs, n_values, batch_size, name_pat, thick = SFM3D_VARIANTS[variant]
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
 
     def return_func(fields, params):
@@ -203,10 +244,9 @@ def train_sfm3d(variant, argv=None):
     sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=_sfm_figure_closure(dm, thick, n_values > 0), learning_rate=3.0e-4)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=1000,
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
-                      default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-3D"),
-                      experiment_name=name_pat.format(i=field_in, o=field_out, c=cropsize),
+                      default_root_dir=log_dir, experiment_name=name,
                       n_val_sampling_steps=int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 100)))
-    trainer.fit(model=sfm, datamodule=dm)
+    trainer.fit(model=sfm, datamodule=dm, ckpt_path=resume)
     return trainer
 
 
@@ -220,6 +260,8 @@ def train_sfm_c_uc_2d(argv=None):
     if len(argv) != 2:
         raise SystemExit("usage: trainSFM_c_uc_from_field_name.py <field_in> <field_out>")
     field_in, field_out = argv
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-2D"), f"LH_c_uc_{field_in}_to_{field_out}"
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -230,9 +272,8 @@ def train_sfm_c_uc_2d(argv=None):
                                     conv_padding_mode="circular", n_attention_heads=4, backend="torch")
     sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=None)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=1000, gradient_clip_val=0.5,
-                      every_n_train_steps=10_000, default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-2D"),
-                      experiment_name=f"LH_c_uc_{field_in}_to_{field_out}", device="cpu")
-    trainer.fit(model=sfm, datamodule=dm)
+                      every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
+    trainer.fit(model=sfm, datamodule=dm, ckpt_path=resume)
     return trainer
 
 
@@ -244,6 +285,8 @@ def train_uc_uc(argv=None):
     if len(argv) != 1:
         raise SystemExit("usage: train_uc_uc_from_field_name.py <field_name>")
     field_name = argv[0]
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"), f"LH_uc_uc_{field_name}"
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -256,9 +299,8 @@ def train_uc_uc(argv=None):
     vdm = vdm_model.LightVDM(score_model=score_model, gamma_min=-13.3, gamma_max=13.3, noise_schedule="learned_linear",
                              draw_figure=None)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=5000, gradient_clip_val=0.5,
-                      every_n_train_steps=10_000, default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"),
-                      experiment_name=f"LH_uc_uc_{field_name}", device="cpu")
-    trainer.fit(model=vdm, datamodule=dm)
+                      every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
+    trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)
     return trainer
 
 
@@ -430,6 +472,8 @@ def train_uc_c(argv=None):
     if len(argv) != 1:
         raise SystemExit("usage: train_uc_c_from_field_name.py <field_name>")
     field_name = argv[0]
+    log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"), f"LH_uc_c_{field_name}"
+    resume = _resume_path(log_dir, name)
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -442,7 +486,6 @@ def train_uc_c(argv=None):
     vdm = vdm_model.LightVDM(score_model=score_model, gamma_min=-13.3, gamma_max=13.3, noise_schedule="learned_linear",
                              draw_figure=None)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=5000, gradient_clip_val=0.5,
-                      every_n_train_steps=10_000, default_root_dir=os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"),
-                      experiment_name=f"LH_uc_c_{field_name}", device="cpu")
-    trainer.fit(model=vdm, datamodule=dm)
+                      every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
+    trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)
     return trainer

@@ -8,10 +8,13 @@ identical weights, ONE all-reduce per step of the flat gradient vector over RCCL
 """
 import json
 import os
+import sys
 import time
 
 import torch
 import torch.distributed as dist
+
+CKPT_FORMAT = 1          # layout of a checkpoint's "trainer_state" (everything beyond the weights that a resumed run needs)
 
 
 def _accepts(fn, name, positional=0):
@@ -87,6 +90,46 @@ def clip_grad_norm_flat_(params, max_norm, use_hip, want_norm=True):
     return total
 
 
+def rng_state(model, device):
+    """Every host-side random stream a training or validation step can draw from, as a dict of plain values (checkpoints): torch's
+    global CPU / device generators (the torch backend's dropout, validation sampling; torch.initial_seed() travels inside the CPU
+    state), the training generators of vdm_model (u0, the Philox seeds), the HIP backend's dropout seed counter, and what the model
+    itself owns (`model.rng_state_dict()`: the torch backend's per-rank noise generator)."""
+    from . import vdm_model
+    st = {"torch_cpu": torch.get_rng_state(), "train_generators": vdm_model.train_generator_states()}
+    dev = torch.device(device)
+    if dev.type == "cuda":
+        st["torch_device"] = torch.cuda.get_rng_state(dev)
+    uh = sys.modules.get(__package__ + ".unet_hip")
+    if uh is not None:
+        st["dropout_seed_counter"] = int(uh._seed_counter[0])
+    if hasattr(model, "rng_state_dict"):
+        st["model"] = model.rng_state_dict()
+    return st
+
+
+def set_rng_state(model, device, st):
+    """Inverse of rng_state(): afterwards every stream continues where the saved run's did."""
+    from . import vdm_model
+    torch.set_rng_state(st["torch_cpu"])
+    dev = torch.device(device)
+    if dev.type == "cuda" and st.get("torch_device") is not None:
+        torch.cuda.set_rng_state(st["torch_device"], dev)
+    vdm_model.set_train_generator_states(st["train_generators"])
+    if "dropout_seed_counter" in st:
+        from . import unet_hip
+        unet_hip._seed_counter[0] = int(st["dropout_seed_counter"])
+    elif __package__ + ".unet_hip" in sys.modules:
+        sys.modules[__package__ + ".unet_hip"]._seed_counter[0] = 0
+    if hasattr(model, "load_rng_state_dict"):
+        model.load_rng_state_dict(st.get("model") or {})
+
+
+def read_checkpoint(path, mmap=False):
+    """A checkpoint file on the host (tensors on the CPU; mmap: mapped, so that reading `global_step` does not read the weights)."""
+    return torch.load(path, map_location="cpu", mmap=bool(mmap), weights_only=True)
+
+
 class GraphedTrainStep:
     """The whole training step - forward diffusion, UNet forward, ELBO, UNet backward, global-norm clip, fused AdamW, weight re-packing -
     captured ONCE in a hipGraph and replayed.  Why: the host needs ~25 us per C-ABI call; in the deep UNet
@@ -96,14 +139,23 @@ class GraphedTrainStep:
     change from replay to replay although the host seeds are baked into the graph), AdamW with capturable state.  Single process only:
     with world > 1 the step stays eager (the RCCL buckets are issued from Python).  The caller must not hold the loss tensor of an
     earlier EAGER step when it builds this object: its autograd graph keeps an AccumulateGrad node bound to the default stream alive,
-    which would run inside the capture (torch warns; the capture then fails)."""
+    which would run inside the capture (torch warns; the capture then fails).
+    Resume: the graph bakes in the host seeds drawn while it is captured, and the warm-up steps draw from the same generators.
+    state_dict() returns the host random streams as they were immediately before construction plus the device counter; built with
+    `state=` of an interrupted run the object first rewinds the streams to that point - the same seeds are baked, the same warm-up
+    draws happen -, puts the caller's streams back afterwards and continues at the saved counter."""
 
-    def __init__(self, model, opt, params, clip_val, batch, warmup=3):
+    def __init__(self, model, opt, params, clip_val, batch, warmup=3, state=None):
         from . import hip_ops as ops
         assert ops.PROFILER is None, "per-launch events cannot be recorded inside a captured graph"
         assert ops.SEED_STEP is None, "another graphed step is being built / run in this process"
         self.model, self.opt, self.params, self.clip = model, opt, params, clip_val
         dev = params[0].device
+        now = None
+        if state is not None:
+            now = rng_state(model, dev)
+            set_rng_state(model, dev, state["rng"])
+        self.rng_before = rng_state(model, dev)
         self.static = {k: ([t.clone() for t in v] if isinstance(v, (list, tuple)) else (None if v is None else v.clone())) for k, v in batch.items()}
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         # The device counter is mixed into the seeds ONLY while this object's own step runs (hip_ops.SEED_STEP is set inside _step and
@@ -113,8 +165,11 @@ class GraphedTrainStep:
         cur = torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
         # eager warm-up (allocator pools, workspaces, packed weights, optimizer state): NOT real steps - parameters, optimizer
-        # moments / step count and the device counter are put back afterwards, so the first replay is optimizer step 1 on this batch
+        # moments / step count and the device counter are put back afterwards, so the first replay continues the optimizer where it
+        # stood (step 1 of a fresh run).  State tensors the warm-up itself created (a fresh optimizer) are zeroed instead, so that
+        # none is created inside the capture.
         keep = [p.detach().clone() for p in params]
+        keep_state = {id(v): (v, v.detach().clone()) for st in opt.state.values() for v in st.values() if torch.is_tensor(v)}
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             for _ in range(warmup):
@@ -124,7 +179,9 @@ class GraphedTrainStep:
                     p.copy_(k)
                 for st in opt.state.values():
                     for v in st.values():
-                        if torch.is_tensor(v):
+                        if torch.is_tensor(v) and id(v) in keep_state:
+                            v.copy_(keep_state[id(v)][1])
+                        elif torch.is_tensor(v):
                             v.zero_()
                 self.counter.zero_()
             sm = getattr(inner, "score_model", None)
@@ -134,11 +191,18 @@ class GraphedTrainStep:
                     sm.repack_weights()
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
-        del keep
+        del keep, keep_state
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.gnorm = self._step()
         self.replays = 0
+        if state is not None:
+            self.counter.fill_(int(state["counter"]))
+            set_rng_state(model, dev, now)
+
+    def state_dict(self):
+        """What a checkpoint keeps of this object (reads the device counter: a host sync - checkpoint steps only)."""
+        return {"counter": int(self.counter.item()), "rng": self.rng_before}
 
     def _step(self):
         from . import hip_ops as ops
@@ -182,24 +246,89 @@ class Trainer:
         self.graph_step = (os.environ.get("VDM4CDM_GRAPH_STEP", "0") != "0") if graph_step is None else bool(graph_step)
         self.global_step = 0
         self.history = []
+        self.optimizers, self.graphed_step = [], None           # set by fit: the optimizer; the GraphedTrainStep if the step was captured
+        self._fit_ctx, self._resumed_from = None, None
 
     def _log(self, rec):
+        if self._resumed_from is not None:                      # the first record of a resumed fit says where it came from
+            rec = {**rec, "resumed_from": self._resumed_from}
+            self._resumed_from = None
         self.history.append(rec)
         if self.rank == 0:
             os.makedirs(self.root, exist_ok=True)
             with open(os.path.join(self.root, "metrics.jsonl"), "a") as f:
                 f.write(json.dumps(rec) + "\n")
 
+    def _trainer_state(self, model, ctx):
+        """Everything beyond the weights that continuing the run needs (the checkpoint's "trainer_state"): optimizer, host random
+        streams, the data module's position, the graphed step's baked-seed record and counter.  Under world > 1 every rank enters ONE
+        all_gather_object with its own small record (its random streams, its data-module state)."""
+        dm, gstep = ctx["datamodule"], ctx["gstep"]
+        rng = rng_state(model, ctx["device"])
+        dm_state = dm.state_dict() if hasattr(dm, "state_dict") else None
+        st = {"format": CKPT_FORMAT, "world": self.world, "optimizer": ctx["opt"].state_dict(), "rng": rng, "datamodule": dm_state,
+              "batches_into_epoch": int(ctx["batches_into_epoch"]), "graph": None if gstep is None else gstep.state_dict()}
+        if self.world > 1:
+            recs = [None] * self.world
+            dist.all_gather_object(recs, {"rank": self.rank, "rng": rng, "datamodule": dm_state})
+            st["ranks"] = recs
+        return st
+
     def save_checkpoint(self, model, epoch):
+        """epoch=E-step=S.ckpt with the reference's keys (state_dict / global_step / epoch: what utils.get_model and generate_3D read)
+        and, when called from fit, "trainer_state".  Written to a temporary file in the same directory and renamed: a job killed
+        while saving leaves no truncated file under the final name."""
+        ctx = self._fit_ctx
+        state = None if ctx is None else self._trainer_state(model, ctx)      # (a collective under world > 1: every rank)
         if self.rank != 0:
             return None
         d = os.path.join(self.root, "checkpoints")
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, f"epoch={epoch}-step={self.global_step}.ckpt")
-        torch.save({"state_dict": model.state_dict(), "global_step": self.global_step, "epoch": epoch}, path)
+        payload = {"state_dict": model.state_dict(), "global_step": self.global_step, "epoch": epoch}
+        if state is not None:
+            payload["trainer_state"] = state
+        tmp = f"{path}.{os.getpid()}.tmp"
+        try:
+            torch.save(payload, tmp)
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
         return path
 
-    def fit(self, model, datamodule):
+    @staticmethod
+    def _read_resume(ckpt_path, datamodule):
+        """Reads a checkpoint for fit(ckpt_path=) and checks, on the host and before any GPU work, that this run can continue it;
+        positions the data module.  Returns (checkpoint, trainer_state, this rank's record)."""
+        path = os.fspath(ckpt_path)
+        if not os.path.isfile(path):
+            raise ValueError(f"fit(ckpt_path={path!r}): no such file")
+        ck = read_checkpoint(path)
+        ts = ck.get("trainer_state") if isinstance(ck, dict) else None
+        if ts is None:
+            raise ValueError(f"{path} is a weights-only checkpoint (keys {sorted(ck) if isinstance(ck, dict) else type(ck).__name__}): it holds "
+                             "no trainer_state - optimizer moments, random streams, data position - so a run cannot be resumed from it "
+                             "(utils.get_model still loads it)")
+        if ts.get("format") != CKPT_FORMAT:
+            raise ValueError(f"{path}: trainer_state format {ts.get('format')!r}, this build reads format {CKPT_FORMAT}")
+        rank, _, world = dist_env()
+        if int(ts["world"]) != world:
+            raise ValueError(f"{path} was written by a run of world size {ts['world']}, this run has world size {world}: a changed "
+                             "world size is not covered by resume (the per-rank random streams and data shards would not line up)")
+        rec = ts["ranks"][rank] if world > 1 else ts
+        if not (hasattr(datamodule, "load_state_dict") and _accepts(datamodule.train_dataloader, "start_batch")):
+            raise ValueError(f"fit(ckpt_path=): the data module {type(datamodule).__name__} has no state_dict() / load_state_dict() / "
+                             "train_dataloader(start_batch=), so the run cannot continue at the batch after the last one consumed")
+        if rec.get("datamodule") is None:
+            raise ValueError(f"{path} holds no data-module state (it was written with a data module without state_dict())")
+        datamodule.load_state_dict(rec["datamodule"])               # (ValueError if it is not the module that wrote the state)
+        return ck, ts, rec
+
+    def fit(self, model, datamodule, ckpt_path=None):
+        """ckpt_path: a checkpoint written by fit - the run continues at its global_step, inside the same epoch at the batch after the
+        last one consumed, bit for bit as if it had never stopped (same world size, batch size and data module)."""
+        resume = None if ckpt_path is None else self._read_resume(ckpt_path, datamodule)
         dev = self.device
         if dev is None:
             dev = "cuda" if torch.cuda.is_available() else "cpu"
@@ -209,6 +338,8 @@ class Trainer:
             dev = f"cuda:{local_rank}"
             torch.cuda.set_device(local_rank)
         model.to(dev)
+        if resume is not None:                                # through the model's own loader: the HIP executor re-packs its weights
+            model.load_state_dict(resume[0]["state_dict"])
         datamodule.device = dev
         params = [p for p in model.parameters() if p.requires_grad]
         if self.world > 1:                                   # identical weights on every rank
@@ -229,50 +360,76 @@ class Trainer:
             if graphed and self.rank == 0:
                 print("Trainer: configure_optimizers() takes no `capturable` argument - the training step stays eager", flush=True)
             opt, graphed = model.configure_optimizers(), False
-        gstep = None
-        epoch, t0 = 0, time.time()
+        self.optimizers = [opt]
+        gstep, graph_state = None, None
+        epoch, t0, start_batch = 0, time.time(), 0
+        if resume is not None:
+            ck, ts, rec = resume
+            graph_state = ts.get("graph")
+            if graph_state is not None and not graphed:
+                raise ValueError(f"{ckpt_path} was written by a run with the graph-captured training step: resume it with graph_step=True "
+                                 "(VDM4CDM_GRAPH_STEP=1), the eager step draws its random numbers differently")
+            how = [{k: g[k] for k in ("capturable", "fused", "foreach") if k in g} for g in opt.param_groups]
+            opt.load_state_dict(ts["optimizer"])
+            for g, h in zip(opt.param_groups, how):          # (how the step is executed belongs to this run, not to the saved state)
+                g.update(h)
+            set_rng_state(model, dev, rec["rng"])
+            self.global_step, epoch, start_batch = int(ck["global_step"]), int(ck["epoch"]), int(ts["batches_into_epoch"])
+            self._resumed_from = os.fspath(ckpt_path)
+            resume = ck = ts = rec = None
+        ctx = self._fit_ctx = {"opt": opt, "datamodule": datamodule, "device": dev, "gstep": None, "batches_into_epoch": 0}
         model.train()
-        while self.global_step < self.max_steps:
-            n_batches = 0
-            for batch in datamodule.train_dataloader(self.rank, self.world):
-                n_batches += 1
-                if graphed and gstep is None and self.max_steps - self.global_step >= 8:
-                    # captured at the first batch (its eager warm-up steps are undone: parameters / optimizer state restored)
-                    gstep = GraphedTrainStep(model, opt, params, self.gradient_clip_val, batch)
-                if gstep is not None and gstep.static["x"].shape == batch["x"].shape:
-                    loss, gnorm = gstep(batch), gstep.gnorm   # one hipGraph replay = the whole step
-                else:                                         # eager step (N > 1 ranks, short runs, a ragged last batch, the torch backend)
-                    loss = model.training_step(batch, self.global_step)
-                    opt.zero_grad(set_to_none=True)
-                    loss.backward()
-                    synced = getattr(sm, "grad_synced", False)     # the HIP backward already averaged the flat UNet gradient (in buckets)
-                    sm.grad_synced = False
-                    for p in params:                              # one collective per remaining parameter tensor (<= 2 schedule scalars)
-                        if p.grad is not None and not (synced and p is getattr(sm, "flat", None)):
-                            allreduce_mean_(p.grad, self.world)
-                    gnorm = None
-                    will_log = (self.global_step + 1) % self.log_every_n_steps == 0 or self.global_step == 0
-                    if self.gradient_clip_val:
-                        gnorm = clip_grad_norm_flat_(params, self.gradient_clip_val, use_hip, want_norm=will_log)
-                    opt.step()
-                self.global_step += 1
-                if self.global_step % self.log_every_n_steps == 0 or self.global_step == 1:
-                    rec = {"step": self.global_step, "epoch": epoch, "lr": opt.param_groups[0]["lr"], "time": time.time() - t0,
-                           "loss": float(loss), **dict(model.logged)}
-                    if gnorm is not None:
-                        rec["grad_norm"] = float(gnorm)
-                    self._log(rec)
-                    if self.enable_progress and self.rank == 0:
-                        print(f"step {self.global_step} loss {rec['loss']:.4f} ({rec['time']:.1f}s)", flush=True)
-                if self.val_check_interval and self.global_step % self.val_check_interval == 0:
-                    self.validate(model, datamodule)
-                if self.every_n_train_steps and self.global_step % self.every_n_train_steps == 0:
-                    self.save_checkpoint(model, epoch)
-                if self.global_step >= self.max_steps:
-                    break
-            if n_batches == 0:
-                raise RuntimeError("empty training dataloader")
-            epoch += 1
+        try:
+            while self.global_step < self.max_steps:
+                n_batches = start_batch                          # (a resumed epoch: the batches the interrupted run consumed count)
+                if start_batch:
+                    loader = datamodule.train_dataloader(self.rank, self.world, start_batch=start_batch)
+                else:
+                    loader = datamodule.train_dataloader(self.rank, self.world)
+                start_batch = 0
+                for batch in loader:
+                    n_batches += 1
+                    if graphed and gstep is None and (graph_state is not None or self.max_steps - self.global_step >= 8):
+                        # captured at the first batch (its eager warm-up steps are undone: parameters / optimizer state restored)
+                        gstep = ctx["gstep"] = GraphedTrainStep(model, opt, params, self.gradient_clip_val, batch, state=graph_state)
+                    if gstep is not None and gstep.static["x"].shape == batch["x"].shape:
+                        loss, gnorm = gstep(batch), gstep.gnorm   # one hipGraph replay = the whole step
+                    else:                                         # eager step (N > 1 ranks, short runs, a ragged last batch, the torch backend)
+                        loss = model.training_step(batch, self.global_step)
+                        opt.zero_grad(set_to_none=True)
+                        loss.backward()
+                        synced = getattr(sm, "grad_synced", False)     # the HIP backward already averaged the flat UNet gradient (in buckets)
+                        sm.grad_synced = False
+                        for p in params:                              # one collective per remaining parameter tensor (<= 2 schedule scalars)
+                            if p.grad is not None and not (synced and p is getattr(sm, "flat", None)):
+                                allreduce_mean_(p.grad, self.world)
+                        gnorm = None
+                        will_log = (self.global_step + 1) % self.log_every_n_steps == 0 or self.global_step == 0
+                        if self.gradient_clip_val:
+                            gnorm = clip_grad_norm_flat_(params, self.gradient_clip_val, use_hip, want_norm=will_log)
+                        opt.step()
+                    self.global_step += 1
+                    if self.global_step % self.log_every_n_steps == 0 or self.global_step == 1:
+                        rec = {"step": self.global_step, "epoch": epoch, "lr": opt.param_groups[0]["lr"], "time": time.time() - t0,
+                               "loss": float(loss), **dict(model.logged)}
+                        if gnorm is not None:
+                            rec["grad_norm"] = float(gnorm)
+                        self._log(rec)
+                        if self.enable_progress and self.rank == 0:
+                            print(f"step {self.global_step} loss {rec['loss']:.4f} ({rec['time']:.1f}s)", flush=True)
+                    if self.val_check_interval and self.global_step % self.val_check_interval == 0:
+                        self.validate(model, datamodule)
+                    if self.every_n_train_steps and self.global_step % self.every_n_train_steps == 0:
+                        ctx["batches_into_epoch"] = n_batches
+                        self.save_checkpoint(model, epoch)
+                    if self.global_step >= self.max_steps:
+                        break
+                if n_batches == 0:
+                    raise RuntimeError("empty training dataloader")
+                epoch += 1
+        finally:
+            self._fit_ctx = None
+        self.graphed_step = gstep                                 # (None: every step of this fit ran eagerly)
         return self
 
     @torch.no_grad()

@@ -827,6 +827,21 @@ def reset_train_generators():
     _TRAIN_GENS.clear()
 
 
+def train_generator_states():
+    """{device: state} of the training generators that exist (checkpoints)."""
+    return {k: g.get_state() for k, g in _TRAIN_GENS.items()}
+
+
+def set_train_generator_states(states):
+    """Inverse of train_generator_states(): exactly the saved generators exist afterwards, each at its saved state; any other is
+    created at its first use from torch.initial_seed(), as in the run that saved them."""
+    _TRAIN_GENS.clear()
+    for k, st in states.items():
+        g = torch.Generator(device=k)
+        g.set_state(st)
+        _TRAIN_GENS[k] = g
+
+
 def noise_seed():
     """A fresh Philox seed for one noise field of the training step (host side; same sequence on every rank - the Philox stream id
     carries the rank)."""
@@ -916,6 +931,21 @@ class LightVDM(nn.Module):
                     sm.repack_weights()
             opt.register_step_post_hook(_after_step)
         return opt
+
+    def rng_state_dict(self):
+        """The random stream this module owns besides the shared training generators: the torch backend's per-rank noise generator
+        (VDM._rank_noise_gen), for checkpoints."""
+        g = getattr(self.model, "_noise_gen", None)
+        if g is None:
+            return {}
+        return {"noise_gen": g.get_state(), "noise_gen_device": str(g.device), "noise_gen_key": [int(k) for k in self.model._noise_gen_key]}
+
+    def load_rng_state_dict(self, state):
+        self.model._noise_gen = None
+        if state.get("noise_gen") is not None:
+            g = torch.Generator(device=state["noise_gen_device"])
+            g.set_state(state["noise_gen"])
+            self.model._noise_gen, self.model._noise_gen_key = g, tuple(int(k) for k in state["noise_gen_key"])
 
     def draw_samples(self, batch_size, n_sampling_steps=250, verbose=False, return_all=False, **kwargs):
         return self.model.sample(batch_size=batch_size, n_sampling_steps=n_sampling_steps, device=self.device,
