@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 14
+#define VDM_ABI_VERSION 15
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -151,9 +151,33 @@ int vdm_conv_dgrad_gn_wgrad(const vdm_conv_desc* d, const void* dout, const void
 /* dw[taps][cout][cin] (fp32) = sum over voxels; workspace holds per-workgroup partial slabs.
  * dbias (optional, ksize 3 only): dbias[cout] = sum over samples and voxels of dout (the conv bias gradient), computed
  * from the dOut tiles the kernel stages anyway.  accumulate != 0 adds to dw / dbias instead of overwriting. */
+/* Workspace: vdm_conv_wgrad needs exactly the `workspace_bytes` of its plan (vdm_conv_wgrad_plan with want_bias = (dbias != NULL)
+ * and the same accumulate) and returns VDM_ERR_ARG for less.  vdm_conv_wgrad_workspace_bytes(d) is the largest of them over the four
+ * (want_bias, accumulate) combinations - those flags change which kernel serves a descriptor - so it is sufficient for any call
+ * with this descriptor; 0 for a bad descriptor. */
 size_t vdm_conv_wgrad_workspace_bytes(const vdm_conv_desc* d);
 int vdm_conv_wgrad(const vdm_conv_desc* d, const void* x, const void* dout, float* dw, float* dbias, int accumulate,
                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* The host-side plan vdm_conv_wgrad follows for this descriptor (ABI v15; csrc/conv_common.h plan_wgrad; host only, no HIP call):
+ * which kernel, its spatial tile, the launch grid and the workspace.  Planning queries, profiling tools and tests read it instead
+ * of restating the rules.  Returns VDM_OK or the status vdm_conv_wgrad would return for the descriptor (VDM_ERR_UNSUPPORTED: fused
+ * bias gradient with ksize 1). */
+#define VDM_WGRAD_THIN_IN 0   /* <= 2 input channels (conv_in): the (tap, channel) pairs are the MFMA's N dimension (csrc/wgrad_thin.hip) */
+#define VDM_WGRAD_THIN_OUT 1  /* one output channel (conv_out), same kernel with the roles of x and dout swapped */
+#define VDM_WGRAD_ROWS 2      /* bf16 3x3x3 stride 1, whole 32-channel blocks: row-reuse kernel over scattered tiles */
+#define VDM_WGRAD_ROWS_ROLL 3 /* the same with a rolling z window: persistent workgroups walk segments of tile columns */
+#define VDM_WGRAD_TAPSPLIT 4  /* generic tap-split kernel (fp32, stride 2, ksize 1, single-16-channel-tile forms) */
+#define VDM_WGRAD_CLASS 5     /* up-sampling conv: 8 parity classes x 8 merged taps on the coarse grid */
+typedef struct {
+    int32_t kernel;          /* VDM_WGRAD_* */
+    int32_t tz, ty;          /* spatial tile (x extent 16); 0 for the thin-side kernels, which walk chunks of 32 voxels along x */
+    int32_t workgroups;      /* launch grid of the main kernel */
+    int32_t tiles;           /* tiles (rolling window: column segments) that the P workgroups of one channel-block pair walk; thin-side: 0 */
+    int32_t P;               /* partial slabs per channel-block pair (= per-pair workgroups); thin-side: slabs in all */
+    size_t workspace_bytes;  /* what vdm_conv_wgrad requires for these (want_bias, accumulate) */
+} vdm_wgrad_plan_info;
+int vdm_conv_wgrad_plan(const vdm_conv_desc* d, int want_bias, int accumulate, vdm_wgrad_plan_info* out);
 
 /* ---- K2: GroupNorm + SiLU (+ dropout) -----------------------------------------------------
  * Replaces torch.group_norm / F.silu / F.dropout [NB normalization.py:273 frame under blocks.py:130].

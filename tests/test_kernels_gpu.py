@@ -972,6 +972,76 @@ def test_last_groupnorm_backward_feeds_conv_in_wgrad(case):
     assert dw1.abs().max().item() > 0
 
 
+# one case per branch of the weight-gradient plan (csrc/conv_common.h plan_wgrad); the expected kernel and plan fields were confirmed
+# with the host-only query.  name, dtype, cin, cout, N, (D,H,W) of dout, ks, stride, ups, circular, bias, accumulate, kernel, plan fields
+WGRAD_PLAN_CASES = [
+    ("rows_roll_z_segments", torch.bfloat16, 32, 32, 1, (8, 8, 16), 3, 1, 0, False, True, False, "ROWS_ROLL", dict(P=2, tiles=2)),       # 1 column x 2 segments, direct reduce
+    ("rows_roll_columns", torch.bfloat16, 256, 256, 1, (8, 24, 48), 3, 1, 0, False, True, False, "ROWS_ROLL", dict(P=8, tiles=9)),       # 64 pairs, P = 8 < 9 columns of one segment
+    ("rows_plain", torch.bfloat16, 256, 256, 1, (4, 24, 48), 3, 1, 0, False, True, False, "ROWS", dict(P=8, tiles=18)),                  # 2 z tiles < 4: no rolling window
+    ("grouped_reduce", torch.bfloat16, 32, 32, 2, (16, 32, 32), 3, 1, 0, False, True, False, "ROWS_ROLL", dict(P=64)),                   # P > 32: grouped slab reduce
+    ("single_tile_cin16", torch.bfloat16, 16, 32, 1, (8, 8, 16), 3, 1, 0, False, True, False, "TAPSPLIT", dict(tz=2, ty=8)),
+    ("single_tile_cout16", torch.bfloat16, 32, 16, 1, (8, 8, 16), 3, 1, 0, False, True, False, "TAPSPLIT", dict(tz=2, ty=8)),
+    ("f32_tapsplit", torch.float32, 32, 32, 1, (8, 8, 16), 3, 1, 0, False, True, False, "TAPSPLIT", dict(tz=2, ty=8, workgroups=16)),
+    ("s2_bf16", torch.bfloat16, 32, 64, 1, (4, 8, 16), 3, 2, 0, False, True, False, "TAPSPLIT", dict(tz=1, ty=4)),
+    ("s2_f32", torch.float32, 32, 64, 1, (4, 8, 16), 3, 2, 0, False, True, False, "TAPSPLIT", dict(tz=1, ty=4)),
+    ("ups", torch.bfloat16, 64, 32, 1, (8, 16, 32), 3, 1, 1, False, True, False, "CLASS", dict(workgroups=32, P=2)),                     # 8 classes x 2 pairs
+    ("k1_no_bias", torch.bfloat16, 64, 32, 1, (8, 8, 16), 1, 1, 0, False, False, False, "TAPSPLIT", dict(tz=4, ty=8)),
+    ("thin_in", torch.bfloat16, 2, 32, 1, (8, 8, 16), 3, 1, 0, False, True, False, "THIN_IN", dict()),
+    ("thin_out", torch.bfloat16, 32, 1, 1, (8, 8, 16), 3, 1, 0, False, False, False, "THIN_OUT", dict()),
+    ("thin_in_circ_ow16", torch.bfloat16, 2, 32, 1, (8, 8, 16), 3, 1, 0, True, True, False, "TAPSPLIT", dict()),                         # circular, 16 wide: generic kernel
+    ("thin_out_accumulate", torch.bfloat16, 32, 1, 1, (8, 8, 16), 3, 1, 0, False, False, True, "TAPSPLIT", dict()),                      # the thin kernel only writes
+]
+
+
+@pytest.mark.parametrize("case", WGRAD_PLAN_CASES, ids=[c[0] for c in WGRAD_PLAN_CASES])
+def test_wgrad_plan_workspace_exact(case):
+    """The workspace contract of vdm_conv_wgrad, per branch of its plan: the case reaches the kernel it names; with EXACTLY the plan's
+    workspace_bytes the launch succeeds, writes nothing behind them (4096 guard bytes) and gives dw / dbias bit-equal to Conv.wgrad
+    with its large cached workspace; with 16 bytes less it is refused before any launch (dw untouched).  The workspace query covers
+    every plan of the descriptor.  (accumulate case: dw starts from fixed values instead of NaN, which no sum survives.)"""
+    import ctypes as C
+    ops, _lib = _ops(), _lib_mod()
+    L = _lib.lib()
+    name, dtype, cin, cout, N, (D, H, W), ks, stride, ups, circ, bias, acc, kernel, fields = case
+    conv = ops.Conv(cin, cout, ks, stride=stride, upsample=ups, circular=circ)
+    d = conv.desc(N, D, H, W, dtype)
+    info = _lib.WgradPlanInfo()
+    assert L.vdm_conv_wgrad_plan(d, int(bias), int(acc), C.byref(info)) == 0
+    assert info.kernel == getattr(_lib, "WGRAD_" + kernel), f"{name}: plan kernel {info.kernel}"
+    for k, v in fields.items():
+        assert getattr(info, k) == v, f"{name}: plan {k} = {getattr(info, k)}, expected {v}"
+    need = info.workspace_bytes
+    assert need > 16 and L.vdm_conv_wgrad_workspace_bytes(d) >= need
+    ishape = (N, 2 * D, 2 * H, 2 * W) if stride == 2 else ((N, D // 2, H // 2, W // 2) if ups else (N, D, H, W))
+    xd = torch.zeros(ishape + (ops.cpad(cin, dtype),), dtype=dtype, device=DEV)
+    xd[..., :cin] = to_dev(rnd(ishape + (cin,), 51, dtype), dtype)
+    dd = torch.zeros((N, D, H, W, ops.cpad(cout, dtype)), dtype=dtype, device=DEV)
+    dd[..., :cout] = to_dev(rnd((N, D, H, W, cout), 52, dtype), dtype)
+
+    def fresh():
+        if acc:
+            return rnd((ks ** 3, cout, cin), 53).to(DEV), (rnd((cout,), 54).to(DEV) if bias else None)
+        return torch.full((ks ** 3, cout, cin), float("nan"), device=DEV), (torch.full((cout,), float("nan"), device=DEV) if bias else None)
+
+    dw_ref, db_ref = fresh()
+    conv.wgrad(xd, dd, dw_ref, db_ref, accumulate=acc)
+    assert not torch.isnan(dw_ref).any()
+    ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    stream = torch.cuda.current_stream().cuda_stream
+    dw, db = fresh()
+    st = L.vdm_conv_wgrad(d, xd.data_ptr(), dd.data_ptr(), dw.data_ptr(), ptr(db), int(acc), ws.data_ptr(), need, stream)
+    torch.cuda.synchronize()
+    assert st == 0, L.vdm_last_error()
+    assert bool((ws[need:] == 0xA5).all()), f"{name}: bytes behind the workspace were written"
+    assert torch.equal(dw, dw_ref) and (db is None or torch.equal(db, db_ref)), f"{name}: differs from Conv.wgrad"
+    dw.fill_(float("nan"))
+    st = L.vdm_conv_wgrad(d, xd.data_ptr(), dd.data_ptr(), dw.data_ptr(), ptr(db), int(acc), ws.data_ptr(), need - 16, stream)
+    torch.cuda.synchronize()
+    assert st != 0 and b"workspace" in L.vdm_last_error()
+    assert bool(torch.isnan(dw).all())
+
+
 # ------------------------------------------------------------------------------------------ fused dgrad (+ folded GroupNorm backward) + wgrad
 DGW_CASES = [  # name, N, (D,H,W), c1, c2 (GroupNorm input = conv input: c1 + c2 = 32), dropout p, circular, bias gradient
     ("l0_like", 2, (16, 64, 128), 32, 0, 0.1, False, True),           # the level-0 shape in small: whole tiles, dropout mask, bias

@@ -49,14 +49,16 @@ def main():
     s = buf.cpu().numpy().reshape(nwg_max, 4, 8).astype(np.int64)
     s = s[s[:, 0, 7] != 0]
     nwg = s.shape[0]
-    tiles_total = args.n * -(-Do // (2 if args.stride == 1 else 2)) * -(-Do // (8 if args.stride == 1 else 4)) * -(-Do // 16) * (-(-cin // 32)) * (-(-cout // 32))
-    per_wg = tiles_total / nwg
+    info = _lib.WgradPlanInfo()                               # the library's own plan of this launch: tile, grid, tiles per workgroup
+    _lib.check(L.vdm_conv_wgrad_plan(conv.desc(args.n, Do, Do, Do, dt), 1, 0, _lib.C.byref(info)), "vdm_conv_wgrad_plan")
+    assert nwg == info.workgroups, f"{nwg} stamped workgroups, the plan launches {info.workgroups}"
+    per_wg = info.tiles / info.P                              # (rolling z window: column segments, each several z steps of the tile)
     us = s[:, :, :6] / 100.0                                  # ticks of 10 ns -> us
     life = (s[:, :, 7] - s[:, :, 6]) / 100.0
     names = ["wait: other waves still read the previous tile", "tile decode + LDS-DMA issue", "DMA landed (vmcnt 0 + barrier)",
              "operand reads + MFMAs", "bias column sums", "slab write (once)"]
     rows = os.environ.get("VDM4CDM_WGRAD_ROWS", "1")
-    print(f"{args.shape} stride {args.stride} N={args.n} WGRAD_ROWS={rows}: {nwg} workgroups x {per_wg:.1f} tiles, launch {e0.elapsed_time(e1) * 1e3:.1f} us "
+    print(f"{args.shape} stride {args.stride} N={args.n} WGRAD_ROWS={rows} kernel {info.kernel} tile {info.tz}x{info.ty}x16: {nwg} workgroups x {per_wg:.1f} tiles, launch {e0.elapsed_time(e1) * 1e3:.1f} us "
           f"(stamped build, incl. the slab reduce), workgroup life {life.mean():.1f} us")
     for k, nm in enumerate(names):
         v = us[:, :, k].reshape(-1)

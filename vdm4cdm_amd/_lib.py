@@ -18,6 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 VDM_F32, VDM_BF16 = 0, 1
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
 PACK_FWD, PACK_DGRAD = 0, 1
+WGRAD_THIN_IN, WGRAD_THIN_OUT, WGRAD_ROWS, WGRAD_ROWS_ROLL, WGRAD_TAPSPLIT, WGRAD_CLASS = range(6)      # VDM_WGRAD_*
 GN_STATS_WS_BYTES = 2048 * 2 * 64 * 4
 
 
@@ -44,6 +45,11 @@ class GnFold(C.Structure):
     _fields_ = [("x1", C.c_void_p), ("x2", C.c_void_p), ("c1", C.c_int32), ("c2", C.c_int32), ("groups", C.c_int32),
                 ("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float), ("inv_keep", C.c_float),
                 ("keep_mask", C.c_void_p), ("partials", C.c_void_p)]
+
+
+class WgradPlanInfo(C.Structure):
+    """vdm_wgrad_plan_info"""
+    _fields_ = [(k, C.c_int32) for k in ("kernel", "tz", "ty", "workgroups", "tiles", "P")] + [("workspace_bytes", C.c_size_t)]
 
 
 class CondMlp(C.Structure):
@@ -73,7 +79,7 @@ PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _T = C.POINTER(DdnmTables)
-ABI_VERSION = 14                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 15                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -98,6 +104,7 @@ SIGNATURES = {
     "vdm_conv_dgrad_gn_wgrad": (_i, [_D, _p, _p, _p, _p, C.POINTER(GnFold), _p, _p, _i, _p, _sz, _p]),
     "vdm_conv_wgrad_workspace_bytes": (_sz, [_D]),
     "vdm_conv_wgrad": (_i, [_D, _p, _p, _p, _p, _i, _p, _sz, _p]),
+    "vdm_conv_wgrad_plan": (_i, [_D, _i, _i, C.POINTER(WgradPlanInfo)]),
     "vdm_gn_stats": (_i, [_p, _i, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p]),
     "vdm_gn_silu_fwd": (_i, [_p, _i, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _f, _f, _u64, _p, _p, _i, _p, _p]),
     "vdm_gn_dyh": (_i, [_p, _i, _p, _i, _i, _i64, _i, _i, _p, _p, _p, _f, _f, _u64, _p, _p, _i, _p, _p]),

@@ -1,4 +1,6 @@
 // conv_api.hip - weight packing kernels and the C-ABI entry points of the convolutions (see conv_common.h).
+#include <algorithm>
+
 #include "conv_common.h"
 
 using namespace vdm;
@@ -240,22 +242,24 @@ extern "C" int vdm_conv_kernel_variant(const vdm_conv_desc* d, int dgrad) {
     return validate(d) ? -1 : plan_of(d, dgrad).family;
 }
 
+// largest workspace over the (want_bias, accumulate) combinations: they change which kernel serves a descriptor
 extern "C" size_t vdm_conv_wgrad_workspace_bytes(const vdm_conv_desc* d) {
     if (validate(d) != VDM_OK) return 0;
-    const int CL = d->dtype == VDM_F32 ? 16 : 32;
-    const int taps = d->ksize * d->ksize * d->ksize;
-    const int cls = d->upsample ? 8 : 1;                   // up-sampling conv: 8 parity classes x 8 merged taps
-    const int npairs = cls * cdiv(d->cout, CL) * cdiv(d->cin, CL);
-    int P = wgrad_wgs() / npairs;
-    if (P < 1) P = 1;
-    const int slots = d->upsample ? 8 : (taps > 1 ? 1 : 4) * taps;
-    size_t need = (size_t)npairs * P * slots * CL * CL * sizeof(float) + (size_t)cdiv(d->cout, CL) * cls * P * CL * sizeof(float);
-    const int thin = wgrad_thin_mode(d->dtype, d->ksize, d->stride, d->upsample, d->cin, d->cout, false, false);
-    if (thin >= 0) {
-        const size_t t = wgrad_thin_workspace_bytes(d->n, d->od, d->oh, d->ow, thin == 0 ? d->cout : d->cin);
-        need = need > t ? need : t;
-    }
+    size_t need = 0;
+    for (int k = 0; k < 4; ++k) need = std::max(need, plan_wgrad(d, (k & 1) != 0, (k & 2) != 0).workspace_bytes);
     return need;
+}
+
+extern "C" int vdm_conv_wgrad_plan(const vdm_conv_desc* d, int want_bias, int accumulate, vdm_wgrad_plan_info* out) {
+    int e = validate(d);
+    if (e) return e;
+    VDM_REQUIRE(out, "conv_wgrad_plan: NULL pointer");
+    const WgradPlan p = plan_wgrad(d, want_bias != 0, accumulate != 0);
+    out->kernel = p.kernel; out->tz = p.tz; out->ty = p.ty;
+    out->workgroups = p.grid; out->tiles = p.ntiles; out->P = p.P;
+    out->workspace_bytes = p.workspace_bytes;
+    if (want_bias && d->ksize == 1) { set_error("conv_wgrad: fused bias gradient is only built for ksize 3"); return VDM_ERR_UNSUPPORTED; }
+    return VDM_OK;
 }
 
 extern "C" int vdm_conv_wgrad(const vdm_conv_desc* d, const void* x, const void* dout, float* dw, float* dbias, int accumulate,
@@ -263,23 +267,23 @@ extern "C" int vdm_conv_wgrad(const vdm_conv_desc* d, const void* x, const void*
     int e = validate(d);
     if (e) return e;
     VDM_REQUIRE(x && dout && dw && workspace, "conv_wgrad: NULL pointer");
-    {   // conv_in / conv_out: one side has <= 2 channels - the (tap, channel) pairs become the MFMA's N dimension (wgrad_thin.hip)
-        static const bool off = getenv("VDM4CDM_NO_THIN_WGRAD") != nullptr;
-        const int thin = off ? -1 : wgrad_thin_mode(d->dtype, d->ksize, d->stride, d->upsample, d->cin, d->cout, dbias != nullptr, accumulate != 0);
-        if (thin >= 0 && !(thin == 1 && dbias) && !(d->pad_mode == VDM_PAD_CIRCULAR && d->ow < 17))
-            return launch_wgrad_thin(thin, x, dout, d->n, d->od, d->oh, d->ow, d->cin, d->cout, d->pad_mode == VDM_PAD_CIRCULAR, dw, dbias, workspace,
-                                     workspace_bytes, (hipStream_t)stream);
+    const WgradPlan p = plan_wgrad(d, dbias != nullptr, accumulate != 0);
+    hipStream_t s = (hipStream_t)stream;
+    if (p.kernel == VDM_WGRAD_THIN_IN || p.kernel == VDM_WGRAD_THIN_OUT) {
+        const bool in = p.kernel == VDM_WGRAD_THIN_IN;       // the dense side is dout (conv_in) or x (conv_out)
+        ThinArgs a{};
+        a.dense = (const bf16_t*)(in ? dout : x);
+        a.N = d->n; a.Dz = d->od; a.Dy = d->oh; a.Dx = d->ow; a.C = in ? d->cout : d->cin; a.circular = d->pad_mode == VDM_PAD_CIRCULAR;
+        return launch_wgrad_thin(a, false, p, in ? x : dout, d->cin, dw, dbias, workspace, workspace_bytes, s);
     }
-    const int CL = d->dtype == VDM_F32 ? 16 : 32;
     WgradArgs w{};
     fill_dims(w.c, d);
     w.c.x = x;
     w.c.Cin = d->cin; w.c.CinStride = cpad(d->cin, d->dtype); w.c.Cout = d->cout;
     w.dout = dout; w.dout_stride = cpad(d->cout, d->dtype);
     w.slabs = (float*)workspace;
-    w.ncb = cdiv(d->cout, CL); w.nkb = cdiv(d->cin, CL);
-    hipStream_t s = (hipStream_t)stream;
-    return launch_wgrad_any(w, dw, dbias, accumulate, d->cout, d->cin, d->ksize, d->stride, d->upsample, workspace_bytes, d->dtype, s);
+    w.ncb = p.ncb; w.nkb = p.nkb;
+    return launch_wgrad_any(w, p, dw, dbias, accumulate, workspace_bytes, d->dtype, s);
 }
 
 

@@ -1394,12 +1394,6 @@ static int s2_tile_z() {
     return v == 1 ? 1 : 2;
 }
 
-// persistent workgroups of a weight-gradient launch over all (cout, cin) block pairs (~2 per CU); VDM4CDM_WGRAD_WGS: experiments
-static int wgrad_wgs() {
-    static const int v = getenv("VDM4CDM_WGRAD_WGS") ? atoi(getenv("VDM4CDM_WGRAD_WGS")) : 512;
-    return v > 0 ? v : 512;
-}
-
 // ---- class-conv tables -----------------------------------------------------------------------
 enum ClsKind { CLS_UP_FWD = 0, CLS_UP_DGRAD = 1, CLS_S2_DGRAD = 2 };
 
@@ -1498,20 +1492,141 @@ static void fill_dims(ConvArgs& a, const vdm_conv_desc* d) {
     a.circular = d->pad_mode == VDM_PAD_CIRCULAR;
 }
 
-// launchers (defined in conv_fwd.hip / conv_cls.hip / conv_wgrad.hip)
+// ---------------------------------------------------------------------------------------------
+// The weight gradient's plan.  plan_wgrad() and the helpers right above it are the only place that decides the kernel, its tile, the
+// number of partial slabs and the workspace of a weight gradient - and the only readers of the VDM4CDM_* switches of that direction.
+// vdm_conv_wgrad, the workspace / plan queries and the launchers (conv_wgrad.hip, wgrad_thin.hip) read the plan.
+// ---------------------------------------------------------------------------------------------
+struct ThinArgs {            // wgrad_thin.hip
+    const bf16_t* dense;     // [N][Dz][Dy][Dx][C]
+    const uint32_t* thin;    // [N][Dz][Dy][Dx]: channels 0..1 of the thin tensor, compacted (thin_compact_kernel)
+    int N, Dz, Dy, Dx, C, circular;
+    float* slabs;            // [gridDim.x][C][80]
+    // GNA (the dense tensor is the RESULT of a GroupNorm backward apply pass that nobody else reads - the gradient at the output of
+    // conv_in): dense = dyh * P + x * Q + R (+ add) is formed in the kernel instead of being written and read back
+    const bf16_t* gx; const bf16_t* gdyh; const bf16_t* gadd;
+    const float* gstats; const float* ggamma; const float* gred; const float* gchan;
+    float* gdgamma; float* gdbeta;
+    int gG; float geps;
+    FastDiv fdx, fdy, fdz;   // divisions of the chunk index by the x chunks per row, Dy, Dz (scalar multiply-high: the index is wave-uniform)
+};
+constexpr int THIN_COLS = 80;                               // 9 rows x 8 + the ones row (72..79)
+
+struct WgradPlan {
+    int kernel;                                  // VDM_WGRAD_*
+    int ks, stride, tz, ty, nta, ntb;            // the kernel instance: taps, tile (TX = 16), real 16-channel tiles of the dOut / input block
+    int CL, ncb, nkb, npairs;                    // channels per 64-byte block; cout blocks, cin blocks, (class,) block pairs
+    int ntz, nty, ntx, ntiles;                   // tile grid; tiles (rolling z: column segments) the workgroups of one pair walk
+    int nseg, zsteps;                            // rolling z: segments per tile column, z steps per segment
+    int P;                                       // persistent workgroups = partial slabs per pair, after every clamp (thin: slabs in all)
+    int per_wg, grouped;                         // slab slots a workgroup writes per tap (ksize 1: one per wave); grouped vs. direct reduce
+    int grid;                                    // workgroups of the main kernel
+    size_t slab_bytes;                           // slabs [pair][P][slot]; behind them the bias partials (thin: the compacted thin tensor)
+    size_t workspace_bytes;
+};
+
+// the switches (experiments, A/B runs; read once per process)
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// persistent workgroups of a weight-gradient launch over all (cout, cin) block pairs (~2 per CU)
+static int wgrad_wgs() { static const int v = env_int("VDM4CDM_WGRAD_WGS", 512); return v > 0 ? v : 512; }
+// persistent workgroups of the thin-side kernel (4 waves each, one chunk per wave in flight ahead of the one it consumes)
+static int wgrad_thin_wgs() { static const int v = env_int("VDM4CDM_THIN_WGS", 512); return v > 0 ? v : 512; }
+static bool wgrad_thin_enabled() { static const bool on = getenv("VDM4CDM_NO_THIN_WGRAD") == nullptr; return on; }
+// VDM4CDM_WGRAD_ROWS=0: the tap-split kernel also for the full bf16 3^3 stride-1 blocks
+static bool wgrad_rows_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROWS", 1) != 0; return on; }
+// VDM4CDM_WGRAD_ROLL=0: no rolling z window - the persistent workgroups of the rows kernel walk scattered tiles, not column segments
+static bool wgrad_roll_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROLL", 1) != 0; return on; }
+// stride 2: 1x4x16 output tiles (57-KB halo, two workgroups per CU; default since round 4: alone 0.100 -> 0.091 / 0.060 -> 0.048 / 0.038 ->
+// 0.034 ms at levels 0 / 1 / 2, step unchanged).  VDM4CDM_S2W_TZ=2: 2x4x16 tiles (95-KB halo, -17 % staged bytes, one workgroup per
+// CU - and none next to a main-stream kernel that holds 2 x 70 KB of the CU's LDS)
+static int wgrad_s2_tile_z() { static const int v = env_int("VDM4CDM_S2W_TZ", 1); return v == 1 ? 1 : 2; }
+// VDM4CDM_GROUPED_REDUCE: the grouped slab reduce also for few slabs (same result, other launch shape)
+static bool wgrad_grouped_only() { static const bool on = getenv("VDM4CDM_GROUPED_REDUCE") != nullptr; return on; }
+
+// thin-side kernel (wgrad_thin.hip): `cdense` channels on the dense side; also the plan of vdm_gn_bwd_apply_wgrad_thin, which has no descriptor
+static WgradPlan plan_wgrad_thin(int kernel, int n, int od, int oh, int ow, int cdense) {
+    WgradPlan p{};
+    p.kernel = kernel; p.ks = 3; p.stride = 1;
+    long long want = ((long long)n * od * oh * cdiv(ow, 32) + 3) / 4;      // chunks of 32 x-consecutive voxels, one per wave
+    if (want > wgrad_thin_wgs()) want = wgrad_thin_wgs();
+    p.grid = p.P = (int)(want < 1 ? 1 : want);
+    p.slab_bytes = (size_t)p.grid * cdense * THIN_COLS * sizeof(float);
+    p.workspace_bytes = p.slab_bytes + (size_t)n * od * oh * ow * sizeof(uint32_t);
+    return p;
+}
+
+static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumulate) {      // d has passed validate()
+    const bool bf16 = d->dtype == VDM_BF16, k3s1 = d->ksize == 3 && d->stride == 1 && !d->upsample;
+    // conv_in / conv_out: one side has <= 2 channels (written, not accumulated; circular padding wraps inside one 32-voxel chunk: ow >= 17)
+    if (bf16 && k3s1 && !accumulate && wgrad_thin_enabled() && !(d->pad_mode == VDM_PAD_CIRCULAR && d->ow < 17)) {
+        const auto dense_ok = [](int c) { return c == 16 || c == 32 || c == 64; };
+        if (d->cin <= 2 && dense_ok(d->cout)) return plan_wgrad_thin(VDM_WGRAD_THIN_IN, d->n, d->od, d->oh, d->ow, d->cout);
+        if (d->cout == 1 && !want_bias && dense_ok(d->cin)) return plan_wgrad_thin(VDM_WGRAD_THIN_OUT, d->n, d->od, d->oh, d->ow, d->cin);
+    }
+    WgradPlan p{};
+    p.kernel = VDM_WGRAD_TAPSPLIT;
+    p.ks = d->ksize; p.stride = d->stride;
+    p.CL = bf16 ? 32 : 16;
+    p.nta = p.ntb = p.CL / 16;
+    p.ncb = cdiv(d->cout, p.CL); p.nkb = cdiv(d->cin, p.CL);
+    p.npairs = p.ncb * p.nkb;
+    p.per_wg = 1;
+    int Dz = d->od, Dy = d->oh, Dx = d->ow, slots = 27, bias_rows = 1;
+    if (d->ksize == 1) {
+        p.tz = 4; p.ty = 8; p.per_wg = 4; slots = 4;
+    } else if (d->stride == 2) {
+        p.tz = wgrad_s2_tile_z(); p.ty = 4;
+    } else if (d->upsample) {                    // 8 parity classes x 8 merged taps, everything on the coarse grid
+        p.kernel = VDM_WGRAD_CLASS;              // (2x4x16 tiles with 1024 workgroups: same time)
+        p.tz = 2; p.ty = 8;
+        Dz /= 2; Dy /= 2; Dx /= 2;
+        p.npairs *= 8; slots = 8; bias_rows = 8;
+    } else {
+        p.tz = 2; p.ty = 8;
+        if (bf16 && d->cin <= 16) p.ntb = 1;     // 64-byte blocks with a single real 16-channel tile
+        else if (bf16 && d->cout <= 16) p.nta = 1;
+        else if (bf16 && wgrad_rows_enabled()) p.kernel = VDM_WGRAD_ROWS;
+    }
+    p.ntz = cdiv(Dz, p.tz); p.nty = cdiv(Dy, p.ty); p.ntx = cdiv(Dx, 16);
+    // validate() bounds a sample's voxels by 2^32 / 4 channels; the batch (<= 2^20) on top of that must still fit the kernels' int tile index
+    const long long ntiles = (long long)d->n * p.ntz * p.nty * p.ntx;
+    p.ntiles = (int)(ntiles < 0x7fffffffLL ? ntiles : 0x7fffffffLL);
+    p.P = wgrad_wgs() / p.npairs;
+    if (p.P < 1) p.P = 1;
+    if (p.P > p.ntiles) p.P = p.ntiles;
+    if (p.kernel == VDM_WGRAD_ROWS && wgrad_roll_enabled()) {
+        const long long ncols = (long long)d->n * p.nty * p.ntx;
+        int nseg = (int)(p.P / ncols);                          // P = the workgroups this pair may use
+        if (nseg > p.ntz / 2) nseg = p.ntz / 2;                 // >= 2 steps per segment, or the walk saves nothing
+        if (nseg >= 1 || p.ntz >= 4) {
+            if (nseg < 1) nseg = 1;                             // more columns than workgroups: a workgroup walks several
+            p.kernel = VDM_WGRAD_ROWS_ROLL;
+            p.zsteps = cdiv(p.ntz, nseg);
+            p.nseg = cdiv(p.ntz, p.zsteps);
+            p.ntiles = (int)(ncols * p.nseg);
+            if (p.P > p.ntiles) p.P = p.ntiles;
+        }
+    }
+    p.grid = p.npairs * p.P;
+    p.grouped = p.P * p.per_wg > 32 || wgrad_grouped_only();
+    p.slab_bytes = (size_t)p.npairs * p.P * slots * p.CL * p.CL * sizeof(float);
+    p.workspace_bytes = p.slab_bytes + (size_t)p.ncb * bias_rows * p.P * p.CL * sizeof(float);
+    return p;
+}
+
+// launchers (defined in conv_fwd.hip / conv_cls.hip / conv_wgrad.hip / wgrad_thin.hip)
 int launch_fwd(const ConvArgs& a, const Plan& p, hipStream_t s);
 int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s);
 int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s);
-// wgrad_thin.hip: weight gradient of conv_in / conv_out (one thin side)
-int wgrad_thin_mode(int dtype, int ksize, int stride, int upsample, int cin, int cout, bool want_bias, bool accumulate);
-size_t wgrad_thin_workspace_bytes(int n, int od, int oh, int ow, int cdense);
-int launch_wgrad_thin(int mode, const void* x, const void* dout, int n, int od, int oh, int ow, int cin, int cout, int circular, float* dw,
-                      float* dbias, void* workspace, size_t workspace_bytes, hipStream_t s);
 int run_cls(const vdm_conv_desc* d, const Plan& p, const void* x, const void* w, const float* bias, const void* res, void* out,
             hipStream_t s, float* gn_partials = nullptr);
 // conv_wgrad.hip: fixed-order fold of the P per-workgroup slabs [P][27][32][32] (+ [P][32] bias partials) of conv_dgw.hip
 int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float* dbias, int P, int accumulate, hipStream_t s);
-int launch_wgrad_any(const WgradArgs& w, float* dw, float* db, int acc, int cout, int cin, int ks, int stride, int ups, size_t ws,
-                     int dtype, hipStream_t s);
+// weight gradient by its plan.  w / a: operands, dims and channel counts; slabs, tile counts and P are the launcher's to fill from the plan
+int launch_wgrad_any(const WgradArgs& w, const WgradPlan& p, float* dw, float* dbias, int accumulate, size_t workspace_bytes, int dtype,
+                     hipStream_t s);
+// gna: the dense operand is formed in the kernel from the GroupNorm backward apply pass (a.g*); thin_src: the tensor with the thin side
+int launch_wgrad_thin(ThinArgs a, bool gna, const WgradPlan& p, const void* thin_src, int cin, float* dw, float* dbias, void* workspace,
+                      size_t workspace_bytes, hipStream_t s);
 
 }  // namespace vdm

@@ -531,152 +531,80 @@ static bool ablate_reduce() {
     return on;
 }
 
-// VDM4CDM_WGRAD_ROWS=0: the tap-split kernel also for the full bf16 3^3 stride-1 blocks (A/B switch)
-static bool wgrad_rows_enabled() {
-    static const bool on = [] { const char* e = getenv("VDM4CDM_WGRAD_ROWS"); return e == nullptr || atoi(e) != 0; }();
-    return on;
-}
-
+// One kernel instance by its plan (conv_common.h plan_wgrad): tile counts and slabs into the arguments, LDS attribute, launch, reduce.
 template <typename T, int KS, int STRIDE, int UPS, int TZ, int TY, int NTA = WG<T>::NT, int NTB = WG<T>::NT>
-static int launch_wgrad_cfg(WgradArgs w, float* dw, float* dbias, int accumulate, int cout, int cin, size_t ws_bytes, hipStream_t s) {
+static int launch_wgrad_cfg(WgradArgs w, const WgradPlan& p, float* dw, float* dbias, int accumulate, hipStream_t s) {
     using G = Geo<KS, STRIDE, TZ, TY>;
-    constexpr int CL = WG<T>::NT * 16;
     ConvArgs& a = w.c;
-    a.ntz = cdiv(a.Dz, TZ); a.nty = cdiv(a.Dy, TY); a.ntx = cdiv(a.Dx, 16);
+    if constexpr (UPS != 0) {                                // the parity classes run on the coarse grid
+        a.Dz /= 2; a.Dy /= 2; a.Dx /= 2;
+        a.Iz = a.Sz = a.Dz; a.Iy = a.Sy = a.Dy; a.Ix = a.Sx = a.Dx;
+    }
+    a.ntz = p.ntz; a.nty = p.nty; a.ntx = p.ntx;
     set_tile_divs(a);
-    w.ntiles = a.N * a.ntz * a.nty * a.ntx;
+    w.ntiles = p.ntiles; w.P = p.P;
 #ifdef VDM_TIMELINE
     a.stamps = g_timeline_stamps;
 #endif
-    const int npairs = w.ncb * w.nkb;
-    int P = wgrad_wgs() / npairs;             // persistent: ~2 workgroups per CU over all (cout, cin) block pairs
-    if (P < 1) P = 1;
-    if (P > w.ntiles) P = w.ntiles;
-    w.P = P;
-    const int per_wg = (G::TAPS > 1) ? 1 : 4;
-    const size_t slab_bytes = (size_t)npairs * P * per_wg * G::TAPS * CL * CL * sizeof(float);
-    const size_t need = slab_bytes + (size_t)w.ncb * P * CL * sizeof(float);
-    if (need > ws_bytes) { set_error("conv_wgrad: workspace too small (%zu < %zu)", ws_bytes, need); return VDM_ERR_ARG; }
-    if (dbias != nullptr && G::TAPS == 1) { set_error("conv_wgrad: fused bias gradient is only built for ksize 3"); return VDM_ERR_UNSUPPORTED; }
-    w.bslabs = dbias ? reinterpret_cast<float*>(reinterpret_cast<char*>(w.slabs) + slab_bytes) : nullptr;
+    w.bslabs = dbias ? reinterpret_cast<float*>(reinterpret_cast<char*>(w.slabs) + p.slab_bytes) : nullptr;
     const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + (size_t)G::OVOX * 64;
-    bool launched = false;
-    if constexpr (sizeof(T) == 2 && KS == 3 && STRIDE == 1 && UPS == 0 && NTA == 2 && NTB == 2) {
-        if (wgrad_rows_enabled()) {
-            // rolling z window (VDM4CDM_WGRAD_ROLL=0: off): the persistent workgroups walk column segments instead of scattered tiles
-            static const bool roll_on = [] { const char* e = getenv("VDM4CDM_WGRAD_ROLL"); return e == nullptr || atoi(e) != 0; }();
-            const int ncols = a.N * a.nty * a.ntx;
-            int nseg = roll_on && TZ == 2 ? P / ncols : 0;               // P = the workgroups this pair may use (slab space is sized for it)
-            if (nseg > a.ntz / 2) nseg = a.ntz / 2;                      // >= 2 steps per segment, or the walk saves nothing
-            if (nseg >= 1 || (roll_on && TZ == 2 && a.ntz >= 4)) {
-                if (nseg < 1) nseg = 1;                                  // more columns than workgroups: a workgroup walks several
-                a.zsteps = cdiv(a.ntz, nseg);
-                a.nseg = cdiv(a.ntz, a.zsteps);
+    constexpr bool ROWS = sizeof(T) == 2 && KS == 3 && STRIDE == 1 && UPS == 0 && NTA == 2 && NTB == 2;
+    if (p.kernel == VDM_WGRAD_ROWS_ROLL || p.kernel == VDM_WGRAD_ROWS) {
+        if constexpr (ROWS) {
+            static unsigned long long lds_done_roll = 0, lds_done_rows = 0;
+            if (p.kernel == VDM_WGRAD_ROWS_ROLL) {          // the persistent workgroups walk column segments instead of scattered tiles
+                a.zsteps = p.zsteps; a.nseg = p.nseg;
                 a.fdz = make_fastdiv((uint32_t)a.nseg);
-                w.ntiles = ncols * a.nseg;
-                if (P > w.ntiles) P = w.ntiles;
-                w.P = P;
                 auto kern = conv_wgrad_rows_kernel<T, TZ, TY, (TZ == 2)>;
-                static unsigned long long lds_done_roll = 0;
                 int e = set_lds(kern, lds, lds_done_roll);
                 if (e) return e;
-                hipLaunchKernelGGL(kern, dim3(npairs * P), dim3(256), lds, s, w);
+                hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), lds, s, w);
             } else {
                 auto kern = conv_wgrad_rows_kernel<T, TZ, TY, false>;
-                static unsigned long long lds_done_rows = 0;
                 int e = set_lds(kern, lds, lds_done_rows);
                 if (e) return e;
-                hipLaunchKernelGGL(kern, dim3(npairs * P), dim3(256), lds, s, w);
+                hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), lds, s, w);
             }
-            launched = true;
         }
-    }
-    if (!launched) {
+    } else {
         auto kern = conv_wgrad_kernel<T, KS, STRIDE, UPS, TZ, TY, NTA, NTB>;
         static unsigned long long lds_done = 0;
         int e = set_lds(kern, lds, lds_done);
         if (e) return e;
-        hipLaunchKernelGGL(kern, dim3(npairs * P), dim3(256), lds, s, w);
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), lds, s, w);
     }
     VDM_LAUNCH_CHECK("conv_wgrad_kernel");
     if (ablate_reduce()) return VDM_OK;
-    const int total = G::TAPS * cout * cin;
-    static const bool grouped_only = getenv("VDM4CDM_GROUPED_REDUCE") != nullptr;      // (same result, other launch shape)
-    if (P * per_wg <= 32 && !grouped_only)
+    const int total = G::TAPS * a.Cout * a.Cin, nslabs = p.P * p.per_wg;
+    if (UPS != 0)
+        hipLaunchKernelGGL(wgrad_cls_reduce_kernel, dim3(cdiv(total, 64)), dim3(256), 0, s, (const float*)w.slabs, dw, a.Cout, a.Cin, w.ncb,
+                           w.nkb, p.CL, p.P, accumulate);
+    else if (!p.grouped)
         hipLaunchKernelGGL(wgrad_reduce_direct_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s,
-                           (const float*)w.slabs, dw, G::TAPS, cout, cin, w.ncb, w.nkb, CL, P * per_wg, accumulate);
+                           (const float*)w.slabs, dw, G::TAPS, a.Cout, a.Cin, w.ncb, w.nkb, p.CL, nslabs, accumulate);
     else
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, WRED_OUT)), dim3(256), 0, s,
-                           (const float*)w.slabs, dw, G::TAPS, cout, cin, w.ncb, w.nkb, CL, P * per_wg, accumulate);
+                           (const float*)w.slabs, dw, G::TAPS, a.Cout, a.Cin, w.ncb, w.nkb, p.CL, nslabs, accumulate);
     VDM_LAUNCH_CHECK("wgrad_reduce_kernel");
     if (dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3(cdiv(cout, 16)), dim3(256), 0, s, (const float*)w.bslabs, dbias, cout, CL, P, accumulate);
+        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3(cdiv(a.Cout, 16)), dim3(256), 0, s, (const float*)w.bslabs, dbias, a.Cout, p.CL,
+                           (UPS != 0 ? 8 : 1) * p.P, accumulate);
         VDM_LAUNCH_CHECK("wgrad_bias_reduce_kernel");
     }
     return VDM_OK;
 }
 
-// up-sampling conv: 8 parity classes x 8 merged taps on the coarse grid
-template <typename T, int TZ, int TY, int WGS>
-static int launch_wgrad_cls(WgradArgs w, float* dw, float* dbias, int accumulate, int cout, int cin, size_t ws_bytes, hipStream_t s) {
-    using G = Geo<3, 1, TZ, TY>;
-    constexpr int CL = WG<T>::NT * 16;
-    ConvArgs& a = w.c;
-    a.Dz /= 2; a.Dy /= 2; a.Dx /= 2;                       // everything runs on the coarse grid
-#ifdef VDM_TIMELINE
-    a.stamps = g_timeline_stamps;
-#endif
-    a.Iz = a.Sz = a.Dz; a.Iy = a.Sy = a.Dy; a.Ix = a.Sx = a.Dx;
-    a.ntz = cdiv(a.Dz, G::TZ); a.nty = cdiv(a.Dy, G::TY); a.ntx = cdiv(a.Dx, 16);
-    set_tile_divs(a);
-    w.ntiles = a.N * a.ntz * a.nty * a.ntx;
-    const int npairs = 8 * w.ncb * w.nkb;
-    int P = (WGS * wgrad_wgs() / 512) / npairs;
-    if (P < 1) P = 1;
-    if (P > w.ntiles) P = w.ntiles;
-    w.P = P;
-    const size_t slab_bytes = (size_t)npairs * P * 8 * CL * CL * sizeof(float);
-    const size_t need = slab_bytes + (size_t)w.ncb * 8 * P * CL * sizeof(float);
-    if (need > ws_bytes) { set_error("conv_wgrad: workspace too small (%zu < %zu)", ws_bytes, need); return VDM_ERR_ARG; }
-    w.bslabs = dbias ? reinterpret_cast<float*>(reinterpret_cast<char*>(w.slabs) + slab_bytes) : nullptr;
-    const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + (size_t)G::OVOX * 64;
-    auto kern = conv_wgrad_kernel<T, 3, 1, 2, TZ, TY>;
-    static unsigned long long lds_done = 0;
-    {
-        int e = set_lds(kern, lds, lds_done);
-        if (e) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(npairs * P), dim3(256), lds, s, w);
-    VDM_LAUNCH_CHECK("conv_wgrad_kernel(class)");
-    if (ablate_reduce()) return VDM_OK;
-    hipLaunchKernelGGL(wgrad_cls_reduce_kernel, dim3(cdiv(27 * cout * cin, 64)), dim3(256), 0, s, (const float*)w.slabs, dw, cout, cin, w.ncb,
-                       w.nkb, CL, P, accumulate);
-    VDM_LAUNCH_CHECK("wgrad_cls_reduce_kernel");
-    if (dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3(cdiv(cout, 16)), dim3(256), 0, s, (const float*)w.bslabs, dbias, cout, CL, 8 * P, accumulate);
-        VDM_LAUNCH_CHECK("wgrad_bias_reduce_kernel");
-    }
-    return VDM_OK;
-}
-
+// plan -> template instance (the kernels are templates over taps, stride, tile and the real 16-channel tiles of a block)
 template <typename T>
-static int launch_wgrad(const WgradArgs& w, float* dw, float* db, int acc, int cout, int cin, int ks, int stride, int ups, size_t ws,
-                        hipStream_t s) {
-    if (ks == 1) return launch_wgrad_cfg<T, 1, 1, 0, 4, 8>(w, dw, db, acc, cout, cin, ws, s);
-    if (stride == 2) {
-        // 1x4x16 output tiles (57-KB halo, two workgroups per CU; default since round 4: alone 0.100 -> 0.091 / 0.060 -> 0.048 / 0.038 ->
-        // 0.034 ms at levels 0 / 1 / 2, step unchanged).  VDM4CDM_S2W_TZ=2: 2x4x16 tiles (95-KB halo, -17 % staged bytes, one workgroup per
-        // CU - and none next to a main-stream kernel that holds 2 x 70 KB of the CU's LDS)
-        static const int tz = [] { const char* e = getenv("VDM4CDM_S2W_TZ"); return e ? atoi(e) : 1; }();
-        if (tz == 1) return launch_wgrad_cfg<T, 3, 2, 0, 1, 4>(w, dw, db, acc, cout, cin, ws, s);
-        return launch_wgrad_cfg<T, 3, 2, 0, 2, 4>(w, dw, db, acc, cout, cin, ws, s);
+static int launch_wgrad(const WgradArgs& w, const WgradPlan& p, float* dw, float* db, int acc, hipStream_t s) {
+    if (p.kernel == VDM_WGRAD_CLASS) return launch_wgrad_cfg<T, 3, 1, 2, 2, 8>(w, p, dw, db, acc, s);
+    if (p.ks == 1) return launch_wgrad_cfg<T, 1, 1, 0, 4, 8>(w, p, dw, db, acc, s);
+    if (p.stride == 2) return p.tz == 1 ? launch_wgrad_cfg<T, 3, 2, 0, 1, 4>(w, p, dw, db, acc, s) : launch_wgrad_cfg<T, 3, 2, 0, 2, 4>(w, p, dw, db, acc, s);
+    if constexpr (sizeof(T) == 2) {
+        if (p.ntb == 1) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 2, 1>(w, p, dw, db, acc, s);
+        if (p.nta == 1) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 1, 2>(w, p, dw, db, acc, s);
     }
-    if (ups) return launch_wgrad_cls<T, 2, 8, 512>(w, dw, db, acc, cout, cin, ws, s);      // (2x4x16 tiles with 1024 workgroups: same time)
-    if constexpr (sizeof(T) == 2) {                          // 64-byte blocks with a single real 16-channel tile
-        if (cin <= 16) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 2, 1>(w, dw, db, acc, cout, cin, ws, s);
-        if (cout <= 16) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 1, 2>(w, dw, db, acc, cout, cin, ws, s);
-    }
-    return launch_wgrad_cfg<T, 3, 1, 0, 2, 8>(w, dw, db, acc, cout, cin, ws, s);
+    return launch_wgrad_cfg<T, 3, 1, 0, 2, 8>(w, p, dw, db, acc, s);
 }
 
 int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float* dbias, int P, int accumulate, hipStream_t s) {
@@ -694,10 +622,12 @@ int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float*
     return VDM_OK;
 }
 
-int launch_wgrad_any(const WgradArgs& w, float* dw, float* db, int acc, int cout, int cin, int ks, int stride, int ups, size_t ws,
-                     int dtype, hipStream_t s) {
-    if (dtype == VDM_F32) return launch_wgrad<float>(w, dw, db, acc, cout, cin, ks, stride, ups, ws, s);
-    return launch_wgrad<bf16_t>(w, dw, db, acc, cout, cin, ks, stride, ups, ws, s);
+int launch_wgrad_any(const WgradArgs& w, const WgradPlan& p, float* dw, float* dbias, int accumulate, size_t workspace_bytes, int dtype,
+                     hipStream_t s) {
+    if (workspace_bytes < p.workspace_bytes) { set_error("conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, p.workspace_bytes); return VDM_ERR_ARG; }
+    if (dbias != nullptr && p.ks == 1) { set_error("conv_wgrad: fused bias gradient is only built for ksize 3"); return VDM_ERR_UNSUPPORTED; }
+    if (dtype == VDM_F32) return launch_wgrad<float>(w, p, dw, dbias, accumulate, s);
+    return launch_wgrad<bf16_t>(w, p, dw, dbias, accumulate, s);
 }
 
 }  // namespace vdm

@@ -12,25 +12,10 @@
 // The D chunk goes through LDS as in gn_skip.hip.  10 MFMAs per 32 voxels (C = 32) instead of 54, the dense tensor streamed once at
 // the HBM rate.  Column 72 is a row of ones: its result column is sum_v D[v][c] (the bias gradient of conv_in).  Per-workgroup slabs,
 // fixed-order reduce + scatter into the master layout: bit-reproducible.  bf16 storage.
-#include "common.h"
+#include "conv_common.h"
 
 namespace vdm {
 
-struct ThinArgs {
-    const bf16_t* dense;     // [N][Dz][Dy][Dx][C]
-    const uint32_t* thin;    // [N][Dz][Dy][Dx]: channels 0..1 of the thin tensor, compacted (thin_compact_kernel)
-    int N, Dz, Dy, Dx, C, circular;
-    float* slabs;            // [gridDim.x][C][80]
-    // GNA (the dense tensor is the RESULT of a GroupNorm backward apply pass that nobody else reads - the gradient at the output of
-    // conv_in): dense = dyh * P + x * Q + R (+ add) is formed in the kernel instead of being written and read back
-    const bf16_t* gx; const bf16_t* gdyh; const bf16_t* gadd;
-    const float* gstats; const float* ggamma; const float* gred; const float* gchan;
-    float* gdgamma; float* gdbeta;
-    int gG; float geps;
-    FastDiv fdx, fdy, fdz;   // divisions of the chunk index by the x chunks per row, Dy, Dz (scalar multiply-high: the index is wave-uniform)
-};
-
-constexpr int THIN_COLS = 80;                               // 9 rows x 8 + the ones row (72..79)
 constexpr int THIN_ROWP = 160;                              // LDS pitch of one L row: 36 positions x 4 B, padded (bank spread)
 
 __device__ __forceinline__ bf16x8 tr16(const char* p0, int second) {
@@ -286,102 +271,38 @@ __global__ void __launch_bounds__(256) wgrad_thin_reduce_kernel(const float* __r
     }
 }
 
-// persistent workgroups (4 waves each, one chunk per wave in flight ahead of the one it consumes).  VDM4CDM_THIN_WGS: A/B
-static int thin_grid(long long nchunks) {
-    static const int cap = [] { const char* e = getenv("VDM4CDM_THIN_WGS"); const int v = e ? atoi(e) : 512; return v > 0 ? v : 512; }();
-    long long want = (nchunks + 3) / 4;
-    if (want > cap) want = cap;
-    return (int)(want < 1 ? 1 : want);
+template <bool CIRC, bool GNA>
+static void launch_thin_kernel(const ThinArgs& a, int grid, hipStream_t s) {
+    switch (a.C) {
+        case 16: hipLaunchKernelGGL((wgrad_thin_kernel<1, CIRC, GNA>), dim3(grid), dim3(256), 0, s, a); break;
+        case 32: hipLaunchKernelGGL((wgrad_thin_kernel<2, CIRC, GNA>), dim3(grid), dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL((wgrad_thin_kernel<4, CIRC, GNA>), dim3(grid), dim3(256), 0, s, a); break;
+    }
 }
 
-// does the thin kernel cover this weight gradient?  returns the mode (0: thin input, 1: thin output) or -1
-int wgrad_thin_mode(int dtype, int ksize, int stride, int upsample, int cin, int cout, bool want_bias, bool accumulate) {
-    if (dtype != VDM_BF16 || ksize != 3 || stride != 1 || upsample || accumulate) return -1;
-    if (cin >= 1 && cin <= 2 && (cout == 16 || cout == 32 || cout == 64)) return 0;
-    if (cout == 1 && !want_bias && (cin == 16 || cin == 32 || cin == 64)) return 1;
-    return -1;
-}
-
-static size_t thin_slab_bytes(int n, int od, int oh, int ow, int cdense) {
-    const long long nchunks = (long long)n * od * oh * ((ow + 31) / 32);
-    return (size_t)thin_grid(nchunks) * cdense * THIN_COLS * sizeof(float);
-}
-
-size_t wgrad_thin_workspace_bytes(int n, int od, int oh, int ow, int cdense) {      // slabs + the compacted thin tensor
-    return thin_slab_bytes(n, od, oh, ow, cdense) + (size_t)n * od * oh * ow * sizeof(uint32_t);
-}
-
-int launch_wgrad_thin(int mode, const void* x, const void* dout, int n, int od, int oh, int ow, int cin, int cout, int circular, float* dw,
-                      float* dbias, void* workspace, size_t workspace_bytes, hipStream_t s) {
-    ThinArgs a{};
-    a.dense = (const bf16_t*)(mode == 0 ? dout : x);
-    const long long nvox = (long long)n * od * oh * ow;
-    uint32_t* compact = reinterpret_cast<uint32_t*>((char*)workspace + thin_slab_bytes(n, od, oh, ow, mode == 0 ? cout : cin));
-    a.thin = compact;
-    a.N = n; a.Dz = od; a.Dy = oh; a.Dx = ow; a.C = mode == 0 ? cout : cin; a.circular = circular;
-    a.slabs = (float*)workspace;
-    if (workspace_bytes < wgrad_thin_workspace_bytes(n, od, oh, ow, a.C)) {
-        set_error("conv_wgrad: workspace too small (vdm_conv_wgrad_workspace_bytes)");
+// a: dims, dense channel count, padding and (plain) the dense operand or (gna: conv_in's weight gradient with the GroupNorm backward
+// apply pass that produces its dense operand folded in) the operands of that pass; the plan gives the grid and the workspace layout
+int launch_wgrad_thin(ThinArgs a, bool gna, const WgradPlan& p, const void* thin_src, int cin, float* dw, float* dbias, void* workspace,
+                      size_t workspace_bytes, hipStream_t s) {
+    if (workspace_bytes < p.workspace_bytes) {
+        set_error("wgrad_thin: workspace too small (%zu < %zu: vdm_conv_wgrad_workspace_bytes)", workspace_bytes, p.workspace_bytes);
         return VDM_ERR_ARG;
     }
-    const long long nchunks = (long long)n * od * oh * ((ow + 31) / 32);
-    if (nchunks + 4 * 4096 >= 0x7fffffffLL || nvox >= 0x7fffffffLL) { set_error("conv_wgrad: tensor too large for the thin-side kernel"); return VDM_ERR_ARG; }
-    a.fdx = make_fastdiv((uint32_t)((ow + 31) / 32)); a.fdy = make_fastdiv((uint32_t)oh); a.fdz = make_fastdiv((uint32_t)od);
-    const int grid = thin_grid(nchunks);
+    const int xchunks = (a.Dx + 31) / 32;
+    const long long nvox = (long long)a.N * a.Dz * a.Dy * a.Dx, nchunks = (long long)a.N * a.Dz * a.Dy * xchunks;
+    if (nchunks + 4 * 4096 >= 0x7fffffffLL || nvox >= 0x7fffffffLL) { set_error("wgrad_thin: tensor too large for the thin-side kernel"); return VDM_ERR_ARG; }
+    a.fdx = make_fastdiv((uint32_t)xchunks); a.fdy = make_fastdiv((uint32_t)a.Dy); a.fdz = make_fastdiv((uint32_t)a.Dz);
+    uint32_t* compact = reinterpret_cast<uint32_t*>((char*)workspace + p.slab_bytes);
+    a.slabs = (float*)workspace;
+    a.thin = compact;
     const long long cb = (nvox + 256 * 8 - 1) / (256 * 8);
-    hipLaunchKernelGGL(thin_compact_kernel, dim3((unsigned)(cb > 4096 ? 4096 : cb)), dim3(256), 0, s, (const bf16_t*)(mode == 0 ? x : dout), nvox, compact);
-    if (circular) {
-        switch (a.C) {
-            case 16: hipLaunchKernelGGL((wgrad_thin_kernel<1, true>), dim3(grid), dim3(256), 0, s, a); break;
-            case 32: hipLaunchKernelGGL((wgrad_thin_kernel<2, true>), dim3(grid), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((wgrad_thin_kernel<4, true>), dim3(grid), dim3(256), 0, s, a); break;
-        }
-    } else {
-        switch (a.C) {
-            case 16: hipLaunchKernelGGL((wgrad_thin_kernel<1, false>), dim3(grid), dim3(256), 0, s, a); break;
-            case 32: hipLaunchKernelGGL((wgrad_thin_kernel<2, false>), dim3(grid), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((wgrad_thin_kernel<4, false>), dim3(grid), dim3(256), 0, s, a); break;
-        }
-    }
+    hipLaunchKernelGGL(thin_compact_kernel, dim3((unsigned)(cb > 4096 ? 4096 : cb)), dim3(256), 0, s, (const bf16_t*)thin_src, nvox, compact);
+    auto launch = a.circular ? (gna ? launch_thin_kernel<true, true> : launch_thin_kernel<true, false>)
+                             : (gna ? launch_thin_kernel<false, true> : launch_thin_kernel<false, false>);
+    launch(a, p.grid, s);
     VDM_LAUNCH_CHECK("wgrad_thin_kernel");
-    hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3(a.C * THIN_COLS / 16), dim3(256), 0, s, (const float*)workspace, grid, a.C, mode, cin, dw, dbias);
-    VDM_LAUNCH_CHECK("wgrad_thin_reduce_kernel");
-    return VDM_OK;
-}
-
-// conv_in's weight gradient with the GroupNorm backward apply pass that produces its dense operand folded in (see ThinArgs)
-int launch_wgrad_thin_gna(const ThinArgs& g, const void* thin_x, int cin, float* dw, float* dbias, void* workspace, size_t workspace_bytes,
-                          hipStream_t s) {
-    ThinArgs a = g;
-    if (workspace_bytes < wgrad_thin_workspace_bytes(a.N, a.Dz, a.Dy, a.Dx, a.C)) {
-        set_error("gn_bwd_apply_wgrad_thin: workspace too small (vdm_conv_wgrad_workspace_bytes of conv_in)");
-        return VDM_ERR_ARG;
-    }
-    const long long nvox = (long long)a.N * a.Dz * a.Dy * a.Dx;
-    const long long nchunks = (long long)a.N * a.Dz * a.Dy * ((a.Dx + 31) / 32);
-    if (nchunks + 4 * 4096 >= 0x7fffffffLL || nvox >= 0x7fffffffLL) { set_error("gn_bwd_apply_wgrad_thin: tensor too large"); return VDM_ERR_ARG; }
-    a.fdx = make_fastdiv((uint32_t)((a.Dx + 31) / 32)); a.fdy = make_fastdiv((uint32_t)a.Dy); a.fdz = make_fastdiv((uint32_t)a.Dz);
-    uint32_t* compact = reinterpret_cast<uint32_t*>((char*)workspace + thin_slab_bytes(a.N, a.Dz, a.Dy, a.Dx, a.C));
-    a.slabs = (float*)workspace;
-    a.thin = compact;
-    const int grid = thin_grid(nchunks);
-    const long long cb = (nvox + 256 * 8 - 1) / (256 * 8);
-    hipLaunchKernelGGL(thin_compact_kernel, dim3((unsigned)(cb > 4096 ? 4096 : cb)), dim3(256), 0, s, (const bf16_t*)thin_x, nvox, compact);
-    if (a.circular) {
-        switch (a.C) {
-            case 16: hipLaunchKernelGGL((wgrad_thin_kernel<1, true, true>), dim3(grid), dim3(256), 0, s, a); break;
-            case 32: hipLaunchKernelGGL((wgrad_thin_kernel<2, true, true>), dim3(grid), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((wgrad_thin_kernel<4, true, true>), dim3(grid), dim3(256), 0, s, a); break;
-        }
-    } else {
-        switch (a.C) {
-            case 16: hipLaunchKernelGGL((wgrad_thin_kernel<1, false, true>), dim3(grid), dim3(256), 0, s, a); break;
-            case 32: hipLaunchKernelGGL((wgrad_thin_kernel<2, false, true>), dim3(grid), dim3(256), 0, s, a); break;
-            default: hipLaunchKernelGGL((wgrad_thin_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, a); break;
-        }
-    }
-    VDM_LAUNCH_CHECK("wgrad_thin_kernel(gna)");
-    hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3(a.C * THIN_COLS / 16), dim3(256), 0, s, (const float*)workspace, grid, a.C, 0, cin, dw, dbias);
+    hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3(a.C * THIN_COLS / 16), dim3(256), 0, s, (const float*)workspace, p.grid, a.C,
+                       p.kernel == VDM_WGRAD_THIN_OUT ? 1 : 0, cin, dw, dbias);
     VDM_LAUNCH_CHECK("wgrad_thin_reduce_kernel");
     return VDM_OK;
 }
@@ -404,5 +325,6 @@ extern "C" int vdm_gn_bwd_apply_wgrad_thin(const void* x, int c, int n, int od, 
     a.N = n; a.Dz = od; a.Dy = oh; a.Dx = ow; a.C = c; a.circular = circular;
     a.gx = (const bf16_t*)x; a.gdyh = (const bf16_t*)dyh; a.gadd = (const bf16_t*)add;
     a.gstats = stats; a.ggamma = gamma; a.gred = red; a.gchan = chan; a.gdgamma = dgamma; a.gdbeta = dbeta; a.gG = groups; a.geps = eps;
-    return launch_wgrad_thin_gna(a, thin_x, thin_c, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_wgrad_thin(a, true, plan_wgrad_thin(VDM_WGRAD_THIN_IN, n, od, oh, ow, c), thin_x, thin_c, dw, dbias, workspace, workspace_bytes,
+                             (hipStream_t)stream);
 }

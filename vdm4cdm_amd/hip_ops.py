@@ -494,11 +494,14 @@ def gn_silu_bwd(x1, x2, groups, stats, gamma, beta, dy, dgamma, dbeta, add1=None
 
 
 def gn_tail_ok(conv_in, x):
-    """Can the last GroupNorm backward + conv_in's weight gradient run as one pass (gn_bwd_fused(..., tail=...))?  bf16, 16 / 32 / 64
-    channels, <= 2 input channels of conv_in, batch <= 16."""
-    return (x.dtype == torch.bfloat16 and x.shape[-1] in (16, 32, 64) and conv_in.ksize == 3 and conv_in.stride == 1 and not conv_in.upsample
-            and conv_in.cin <= 2 and conv_in.cout == x.shape[-1] and x.shape[0] <= 16 and (not conv_in.circular or x.shape[3] >= 17)
-            and "VDM4CDM_NO_THIN_WGRAD" not in _os.environ and _os.environ.get("VDM4CDM_FUSED_TAIL", "1") != "0")
+    """Can the last GroupNorm backward + conv_in's weight gradient run as one pass (gn_bwd_fused(..., tail=...))?  Where the plan of
+    conv_in's weight gradient (with bias, written) is the thin-input kernel, at batch <= 16."""
+    if conv_in.cout != x.shape[-1] or x.shape[0] > 16 or _os.environ.get("VDM4CDM_FUSED_TAIL", "1") == "0":
+        return False
+    info = _lib.WgradPlanInfo()
+    n, od, oh, ow, _ = x.shape
+    check(_lib.lib().vdm_conv_wgrad_plan(conv_in.desc(n, od, oh, ow, x.dtype), 1, 0, C.byref(info)), "vdm_conv_wgrad_plan")
+    return info.kernel == _lib.WGRAD_THIN_IN
 
 
 def gn_bwd_fused(x1, x2, groups, stats, gamma, dyh, dgamma, dbeta, add1=None, add2=None, colsum=None, dx1=None, dx2=None, skip=None, tail=None):
