@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 15
+#define VDM_ABI_VERSION 16
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -358,6 +358,17 @@ typedef struct {
 } vdm_augment_sample;
 int vdm_augment_batch(const vdm_augment_channel* host_channels, int n_channels, int fullsize, int crop,
                       const vdm_augment_sample* host_samples, int n_samples, void* stream);
+
+/* ---- data preparation: trilinear down-gridding of the cube stacks on the device ---------------------------------------------------
+ * Replaces the data-preparation notebook [REF scripts/make_down_grids.ipynb cell 3], which turns the 256^3 CAMELS stacks into the
+ * 3D_grids_<T> training sets with torch.nn.functional.interpolate(stack[:, None], size=T, mode="trilinear", align_corners=False):
+ *   per axis and output index d: coordinate max((d + 1/2) S/T - 1/2, 0), i0 = floor, i1 = min(i0 + 1, S - 1), lambda = frac
+ *   (edges clamped, not periodic), out = the 8-corner blend with weights (1 - lambda | lambda) per axis.
+ * i0 and lambda are taken from the exact rational ((2d + 1) S - T) / (2T) in integer arithmetic (lambda = remainder / 2T rounded once to
+ * fp32); the blend is fp32 in a fixed order (z, y, x) without atomics: equal inputs give equal bits on every call, T == S is a
+ * bit-exact copy.  src: [n][S][S][S] fp32, dst: [n][T][T][T] fp32 (x fastest), 1 <= T <= S <= 1024; S, T multiples of 4 and 16-byte
+ * aligned pointers take the path with 16-byte loads and stores.  n == 0 is a successful no-op. */
+int vdm_downgrid_trilinear(const float* src, float* dst, int64_t n, int S, int T, void* stream);
 
 /* ---- attention block of the mid level (CUNet(mid_attn=True, n_attention_heads)) [REF trainSFM_c_uc_from_field_name.py:61,104-118;
  * NB blocks.py:169-170 `x = self.attention_blocks[i](x)`] ---------------------------------------------------------------------

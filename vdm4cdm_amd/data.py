@@ -131,6 +131,8 @@ ALPHAS = {"Mcdm": 1.0, "Mstar": 1.0, "B": 1.0, "HI": 1.0, "Mgas": 1.0, "MgFe": 1
 NORMALIZATIONS = {"Mcdm": (10.019186475678042, 0.5520203178284999), "Mstar": (0.010429391444558287, 0.3219291117577123),
                   "Go7": (0.0, 1.0), "Go8": (0.0, 1.0), "Go9": (0.0, 1.0)}
 DATA_ROOT_ENV = "VDM4CDM_DATA_ROOT"
+# "1": a missing 3D_grids_<S> set is derived in HBM from the 256^3 stack (trilinear, as make_down_grids writes it) instead of failing
+DOWNGRID_ENV = "VDM4CDM_DOWNGRID"
 
 
 def grid_size(dataset_name):
@@ -146,6 +148,23 @@ def field_path(root, dataset_name, suite_name, set_name, z_name, channel_name):
     sub = "3D_grids_new" if S == 256 else f"3D_grids_{S}"
     z = z_name.split("_", 1)[1]
     return os.path.join(root, sub, f"Grids_{channel_name}_{suite_name}_{set_name}_{S}_z={z}.npy")
+
+
+def down_grid_edge(nside, s_file):
+    """Edge T of the down-gridded cubes of data set CMD_<nside> made from a "256" stack whose cubes really have edge `s_file`:
+    T = nside * s_file / 256 (CAMELS: s_file == 256, T == nside; a small stand-in stack keeps the ratio).  ValueError unless 1 <=
+    nside <= 256 and T is an integer."""
+    if isinstance(nside, bool) or not isinstance(nside, (int, np.integer)) or not 1 <= nside <= 256:
+        raise ValueError(f"down-gridding: nside = {nside!r} must be an integer in 1..256")
+    if (int(nside) * int(s_file)) % 256:
+        raise ValueError(f"down-gridding: nside = {nside} of a source stack with edge {s_file} gives the non-integer edge "
+                         f"{nside * s_file / 256:g} (T = nside * edge / 256)")
+    return int(nside) * int(s_file) // 256
+
+
+def _slab_sims(f):
+    """Whole simulations per upload slab: at most 1 GiB of the stack `f`, at least one cube."""
+    return max(1, (1 << 30) // max(1, f[0].nbytes))
 
 
 def params_path(root, suite_name, set_name):
@@ -184,18 +203,34 @@ class AstroDataModule:
         sel = selection
         cv = sel["set_name"] == "CV"
         self.fields = []
+        self._derived_edge = []                  # per channel: None (the file has the data set's size) or the edge to down-grid to
         for c in self.channel_names:
             # always memory-mapped, whatever `mmap` says (the reference's scripts pass mmap=False and hold the whole set - 67 GB per field at
             # 256^3 - in host RAM, once per rank): here the cubes live in HBM after _resident() uploaded them slab by slab, the host only
             # ever touches one slab
-            f = np.load(field_path(root, sel["dataset_name"], sel["suite_name"], sel["set_name"], sel["z_name"], c), mmap_mode="r")
+            path = field_path(root, sel["dataset_name"], sel["suite_name"], sel["set_name"], sel["z_name"], c)
+            edge = None
+            if os.environ.get(DOWNGRID_ENV) == "1" and grid_size(sel["dataset_name"]) != 256 and not os.path.exists(path):
+                # opt-in: the resampled set is not on disk - open the 256^3 stack instead; _resident() down-grids every slab it uploads
+                src = field_path(root, "CMD", sel["suite_name"], sel["set_name"], sel["z_name"], c)
+                if not os.path.exists(src):
+                    raise FileNotFoundError(f"{path} does not exist and ${DOWNGRID_ENV}=1 cannot derive it: the 256^3 stack {src} is missing too")
+                f = np.load(src, mmap_mode="r")
+                edge = down_grid_edge(grid_size(sel["dataset_name"]), f.shape[-1])
+                print(f"[data] {c}: {sel['dataset_name']} is derived on the device from {src} (trilinear {f.shape[-1]} -> {edge}, "
+                      f"${DOWNGRID_ENV}=1)", flush=True)
+            else:
+                f = np.load(path, mmap_mode="r")
             self.fields.append(f[_cv_keep(len(f))] if cv else f)
+            self._derived_edge.append(edge)
         self.params = np.atleast_2d(np.loadtxt(params_path(root, sel["suite_name"], sel["set_name"]))).astype(np.float32)
         if cv:
             self.params = self.params[_cv_keep(len(self.params))]
-        self.fullsize = int(self.fields[0].shape[-1])
-        for f in self.fields:
-            assert f.ndim == 4 and f.shape[1:] == (self.fullsize,) * 3 and len(f) == len(self.fields[0]), "field shapes disagree"
+        edges = [int(f.shape[-1]) if e is None else e for f, e in zip(self.fields, self._derived_edge)]
+        self.fullsize = edges[0]
+        for f, e in zip(self.fields, edges):
+            assert f.ndim == 4 and f.shape[1:] == (f.shape[-1],) * 3 and e == self.fullsize and len(f) == len(self.fields[0]), \
+                "field shapes disagree"
         assert len(self.params) == len(self.fields[0]), f"len(params)={len(self.params)} != len(fields)={len(self.fields[0])}"
         self.crop = cropsize if do_crop else self.fullsize
         ax = np.arange(0, self.fullsize, self.crop)
@@ -247,11 +282,21 @@ class AstroDataModule:
             if dev.type != "cuda":
                 raise RuntimeError("AstroDataModule builds its batches with a HIP kernel: set .device to a GPU (there is no CPU path)")
             self._dev_fields = []
-            for f in self.fields:                             # upload in slabs of simulations: the (memory-mapped) 256^3 sets are
-                d = torch.empty(f.shape, dtype=torch.float32, device=dev)      # 67 GB per field - never a second full copy on the host
-                step = max(1, (1 << 30) // max(1, f[0].nbytes))
-                for i in range(0, len(f), step):
-                    d[i:i + step].copy_(torch.from_numpy(np.ascontiguousarray(f[i:i + step], dtype=np.float32)))
+            for f, edge in zip(self.fields, self._derived_edge):  # upload in slabs of simulations: the (memory-mapped) 256^3 sets are
+                step = _slab_sims(f)                                       # 67 GB per field - never a second full copy on the host
+                if edge is None:
+                    d = torch.empty(f.shape, dtype=torch.float32, device=dev)
+                    for i in range(0, len(f), step):
+                        d[i:i + step].copy_(torch.from_numpy(np.ascontiguousarray(f[i:i + step], dtype=np.float32)))
+                else:                             # derived set: every slab of the 256^3 stack is down-gridded straight into the resident stack
+                    from . import hip_ops as ops
+                    d = torch.empty((len(f),) + (edge,) * 3, dtype=torch.float32, device=dev)
+                    slab = torch.empty((min(step, len(f)),) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)
+                    for i in range(0, len(f), step):
+                        k = min(step, len(f) - i)
+                        slab[:k].copy_(torch.from_numpy(np.ascontiguousarray(f[i:i + k], dtype=np.float32)))
+                        ops.downgrid_trilinear(slab[:k], edge, out=d[i:i + k])
+                    del slab
                 self._dev_fields.append(d)
             self._dev_params = torch.from_numpy(self.params).to(dev)
         return self._dev_fields
@@ -384,6 +429,85 @@ def write_synthetic_camels(root, dataset_name="CMD_128", suite_name="Astrid", se
     os.makedirs(os.path.dirname(params_path(root, suite_name, set_name)), exist_ok=True)
     np.savetxt(params_path(root, suite_name, set_name), params)
     return root
+
+
+def make_down_grids(root, nside, fields=("Mcdm", "Mstar"), sets=("LH", "CV", "1P"), suite="Astrid", z="z_0.0", overwrite=False,
+                    device=None, verbose=True):
+    """The reference's data-preparation step (scripts/make_down_grids.ipynb) on the device: every 256^3 stack
+    3D_grids_new/Grids_<field>_<suite>_<set>_256_z=....npy below `root` becomes the float32 stack (n, T, T, T) of data set
+    CMD_<nside> at ``field_path(root, f"CMD_{nside}", ...)``, T = nside * (edge found in the source) / 256, resampled by
+    ``vdm_downgrid_trilinear`` (F.interpolate(mode="trilinear", align_corners=False) semantics).  The defaults are the six stacks the
+    notebook converts; the parameter tables are shared between the sizes, so nothing else is written.
+
+    Every source is checked first - a missing one, an `nside` outside 1..256 or a non-integer T raises ValueError before any GPU
+    work.  A stack is uploaded in slabs of whole simulations (<= 1 GiB), resampled, and copied back into a temporary file of the target
+    directory that replaces the final name only when complete: an interrupted run never leaves a truncated .npy.  An existing target is
+    kept unless `overwrite`.  Returns one record per stack: {"path", "status" ("written" | "kept"), "shape", "seconds": {"read", "h2d",
+    "kernel", "d2h", "write"}} (the phases are separated by device synchronisations: this is a tool, not the training path)."""
+    import time
+    if not root:
+        raise ValueError(f"make_down_grids needs the CAMELS directory (root= or ${DATA_ROOT_ENV})")
+    down_grid_edge(nside, 256)                              # (the range of nside, whatever the sources hold)
+    plan = []
+    for c in fields:
+        for set_name in sets:
+            src = field_path(root, "CMD", suite, set_name, z, c)
+            if not os.path.exists(src):
+                raise ValueError(f"make_down_grids: the 256^3 source stack {src} does not exist")
+            f = np.load(src, mmap_mode="r")
+            if f.ndim != 4 or f.shape[1:] != (f.shape[-1],) * 3:
+                raise ValueError(f"make_down_grids: {src} has shape {f.shape}, not a stack of cubes (n, S, S, S)")
+            plan.append((src, f, down_grid_edge(nside, f.shape[-1]), field_path(root, f"CMD_{nside}", suite, set_name, z, c)))
+    dev = torch.device(device if device is not None else "cuda")
+    report = []
+    for src, f, T, dst in plan:
+        shape = (len(f), T, T, T)
+        if os.path.exists(dst) and not overwrite:
+            report.append({"path": dst, "status": "kept", "shape": shape, "seconds": {}})
+            if verbose:
+                print(f"[make_down_grids] {dst} exists: kept (--overwrite rewrites it)", flush=True)
+            continue
+        from . import hip_ops as ops
+        sec = dict.fromkeys(("read", "h2d", "kernel", "d2h", "write"), 0.0)
+
+        def lap(key, t0):
+            torch.cuda.synchronize(dev)
+            sec[key] += time.perf_counter() - t0
+            return time.perf_counter()
+
+        os.makedirs(os.path.dirname(dst), exist_ok=True)
+        tmp = os.path.join(os.path.dirname(dst), f".{os.path.basename(dst)}.tmp{os.getpid()}")
+        try:
+            out = np.lib.format.open_memmap(tmp, mode="w+", dtype=np.float32, shape=shape)
+            step = _slab_sims(f)
+            slab = torch.empty((min(step, len(f)),) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)
+            small = torch.empty((slab.shape[0], T, T, T), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                for i in range(0, len(f), step):
+                    k = min(step, len(f) - i)
+                    t0 = time.perf_counter()
+                    host = torch.from_numpy(np.array(f[i:i + k], dtype=np.float32))      # (a copy: the read happens here, not in the upload)
+                    t0 = lap("read", t0)
+                    slab[:k].copy_(host)
+                    t0 = lap("h2d", t0)
+                    ops.downgrid_trilinear(slab[:k], T, out=small[:k])
+                    t0 = lap("kernel", t0)
+                    back = small[:k].cpu().numpy()
+                    t0 = lap("d2h", t0)
+                    out[i:i + k] = back
+                    lap("write", t0)
+            t0 = time.perf_counter()
+            out.flush()
+            del out
+            os.replace(tmp, dst)
+            sec["write"] += time.perf_counter() - t0
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        report.append({"path": dst, "status": "written", "shape": shape, "seconds": sec})
+        if verbose:
+            print(f"[make_down_grids] {src} -> {dst} {shape}: " + ", ".join(f"{k} {v:.2f} s" for k, v in sec.items()), flush=True)
+    return report
 
 
 def get_dataset(dataset_name="CMD_128", suite_name="Astrid", return_func=None, set_name="LH", z_name="z_0.0",

@@ -665,6 +665,21 @@ def augment_batch(fields, consts, samples, crop, out=None):
     return out
 
 
+def downgrid_trilinear(src, T, out=None):
+    """Trilinear down-gridding on the device (vdm_downgrid_trilinear): src = cube stack [n, S, S, S] fp32 on the GPU -> [n, T, T, T] with
+    the semantics of F.interpolate(src[:, None], size=T, mode="trilinear", align_corners=False), index and weight from the exact ratio."""
+    assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 4 and \
+        src.shape[1] == src.shape[2] == src.shape[3], "the source must be a contiguous fp32 [n, S, S, S] tensor on the GPU"
+    n, S, T = src.shape[0], src.shape[-1], int(T)
+    if out is None:
+        out = torch.empty((n, T, T, T), dtype=torch.float32, device=src.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, T, T, T), \
+        f"out must be a contiguous fp32 [{n}, {T}, {T}, {T}] tensor on the GPU"
+    if n:                                                   # (an empty tensor has no storage to point at)
+        check(_lib.lib().vdm_downgrid_trilinear(_p(src), _p(out), n, S, T, _s()), "vdm_downgrid_trilinear")
+    return out
+
+
 def channel_sums(x, out):
     """out[c] (fp32 view) = sum over all leading dims of x[..., c]."""
     _contig(x, out)
