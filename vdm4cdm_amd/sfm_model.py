@@ -15,13 +15,14 @@ Lipman et al. 2023 / Tong et al. 2023 (I-CFM) on the straight path between the p
     sample: x <- x + v_theta(x, t_i; x0, v) / n,  t_i = i / n, starting from x = x0       (explicit Euler, n steps)
 
 On the HIP backend the interpolation / target are the K7 kernel (``vdm_diffuse``: a x + b y per sample), the loss and its
-gradient the K8 kernel, and the Euler loop is the same captured hipGraph as the VDM sampler (``hip_graph_sampler``) with the
-coefficient table {1, -1/n, 0, t_i}.
+gradient the K8 kernel, and the Euler loop is the same captured hipGraph as the VDM sampler (``sampling.hip_graph_sampler``) with
+the coefficient table {1, -1/n, 0, t_i}.
 """
 import torch
 import torch.nn as nn
 
-from .vdm_model import _DiffusionLossFn, hip_graph_sampler, stratified_times
+from .sampling import ChainNoise, hip_graph_sampler
+from .vdm_model import _DiffusionLossFn, stratified_times
 
 
 class SFM(nn.Module):
@@ -86,7 +87,8 @@ class SFM(nn.Module):
         if self._hip(x) and not return_all:
             coef = self.step_table(n_sampling_steps).to(device=x.device, dtype=torch.float32).contiguous()
             s_cond = x0 if getattr(self.velocity_model, "s_conditioning_channels", 1) else None
-            return hip_graph_sampler(self.velocity_model, x, coef, None, 0, verbose, use_graph, s_cond, list(v_conditionings or []))
+            noise = ChainNoise("sample", x.shape[0], x.shape[1:], x.device, seed=0)       # (scale = 0: the update adds no noise)
+            return hip_graph_sampler(self.velocity_model, x, coef, noise, verbose, use_graph, s_cond, list(v_conditionings or []))
         xs = []
         for i in range(n_sampling_steps):
             t = torch.full((x.shape[0],), i / n_sampling_steps, device=x.device)

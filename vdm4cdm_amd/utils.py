@@ -188,7 +188,7 @@ def get_ddnm_result(vdm, y, A=None, AT=None, n_sampling_steps=250, l=10, return_
                     noises=None, operator=None, use_graph=True, stats=None, **kwargs):
     """DDNM range/null-space sampler with time travel (length l), on this package's VDM.
     Without seed / seeds / noises / operator: the reference's loop as it stands (global torch RNG, eager evaluations).
-    With any of them: the seed- or noise-keyed sampler (vdm_model.ddnm_sample) - on the HIP backend one replayed hipGraph per network
+    With any of them: the seed- or noise-keyed sampler (sampling.ddnm_sample) - on the HIP backend one replayed hipGraph per network
     evaluation with the DDNM update as HIP kernels.  seeds: one int per row of y, every row a chain of its own (its result does not
     depend on the batch it sits in); seed: one stream for the whole batch; noises: every field in call order, z_1 first;
     operator: a MaskOperator / BlockMeanOperator (A and AT may then be omitted; the update is one fused kernel); generic A / AT
@@ -197,7 +197,7 @@ def get_ddnm_result(vdm, y, A=None, AT=None, n_sampling_steps=250, l=10, return_
     tools ({"graph", "evaluations", "allocated_before", "allocated_after"}: whether a captured step was replayed, the number of
     network evaluations, torch.cuda.memory_allocated before the first and after the last evaluation); nothing is recorded without it."""
     if seed is not None or seeds is not None or noises is not None or operator is not None:
-        from .vdm_model import ddnm_sample
+        from .sampling import ddnm_sample
         return ddnm_sample(vdm.model, y, A, AT, operator, n_sampling_steps, l, return_all, verbose, seed, seeds, noises, use_graph,
                            vdm.device, kwargs, stats)
     if A is None or AT is None:

@@ -12,7 +12,7 @@ The arithmetic is spec D9-D12 of SURVEY.md section 8 (the mltools source is not 
 
 On a GPU with the HIP backend the forward diffusion, the ELBO reductions and the ancestral update are the
 HIP kernels K7-K9 and the denoise step is captured once in a hipGraph and replayed for every step
-(per-step scalars come from a device table indexed by a device-side step counter).
+(per-step scalars come from a device table indexed by a device-side step counter): vdm4cdm_amd.sampling, whose names stay importable here.
 """
 import math
 
@@ -21,6 +21,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import os
+
+from .sampling import ChainNoise, ddnm_lengths, ddnm_sample, ddnm_schedule, hip_ddnm_sampler, hip_graph_sampler  # noqa: F401
 
 DATA_NOISE = 1.0e-3
 # Fused head of the HIP training step (vdm_diffuse_pack + vdm_loss_terms_rng; VDM4CDM_FUSED_HEAD=0: randn -> diffuse -> pack_input, A/B)
@@ -416,23 +418,15 @@ class VDM(nn.Module):
         `seeds` (one int per row): every row is a chain of its own, keyed by its seed wherever it sits in the batch - row r draws z_1
         and its step noise exactly as a batch-1 chain with seed=seeds[r] does (a supplied z: the seeds key the step noise only).
         `seed` with batch_size > 1 keeps its meaning of one stream for the whole batch."""
-        if seeds is not None:
-            seeds = [int(s) for s in seeds]
-            if len(seeds) != batch_size:
-                raise ValueError(f"sample: {len(seeds)} seeds for batch_size={batch_size} (one seed per chain)")
-            if seed is not None or noises is not None:
-                raise ValueError("sample: seeds= cannot be combined with seed= or noises=")
-        shape = (batch_size, *self.score_model.shape)
-        if z is None and seeds is not None:
-            z = torch.cat([torch.randn((1, *self.score_model.shape), generator=torch.Generator().manual_seed(s)) for s in seeds]).to(device)
-        elif z is None:
-            z = torch.randn(shape, device=device) if seed is None else \
-                torch.randn(shape, generator=torch.Generator().manual_seed(int(seed))).to(device)
-        else:
-            z = z.clone()                                    # the HIP path updates z in place: never the caller's tensor
-        z = z.to(device=device, dtype=torch.float32).contiguous()
+        noise = ChainNoise("sample", batch_size, self.score_model.shape, device, seed, seeds, noises)
+        z = noise.z1(z)
         if self._hip(z):                                     # (return_all: the same captured step, z copied out after every replay)
-            return self._sample_hip(z, n_sampling_steps, noises, seed, verbose, use_graph, kwargs, return_all, seeds)
+            coef = self.step_table(n_sampling_steps).to(device=z.device, dtype=torch.float32).contiguous()
+            cfg = self.w_cfg is not None and not self.training
+            assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+            return hip_graph_sampler(self.score_model, z, coef, noise, verbose, use_graph, kwargs.get("s_conditioning"),
+                                     list(kwargs.get("v_conditionings") or []), w_cfg=float(self.w_cfg) if cfg else None,
+                                     mask_fn=self.cfg_mask, return_all=return_all)
         steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1, device=device)
         zs = []
         rng = range(n_sampling_steps)
@@ -442,366 +436,16 @@ class VDM(nn.Module):
                 rng = trange(n_sampling_steps, desc="sampling")
             except ImportError:
                 pass
-        gen = gens = None
-        if noises is None and seed is not None:              # a seeded chain is reproducible on this path too (per-step noise from
-            gen = torch.Generator().manual_seed(int(seed) + 1)   # the chain's own generator, not the global RNG)
-        if seeds is not None:                                # per-chain seeds: every row its own generator, a (1, ...) draw per step
-            gens = [torch.Generator().manual_seed(s + 1) for s in seeds]
         for i in rng:
-            if noises is None and gen is None and gens is None:
+            if not noise.keyed:
                 z = self.sample_zs_given_zt(zt=z, t=steps[i], s=steps[i + 1], **kwargs)
-            else:
+            else:                                            # a keyed chain is reproducible on this path too (not the global RNG)
                 w_z, w_x, x0, scale = self.sample_zs_given_zt(zt=z, t=steps[i], s=steps[i + 1], return_ddnm=True, **kwargs)
-                if noises is not None:
-                    eps = noises[i].to(z)
-                elif gens is not None:
-                    eps = torch.cat([torch.randn((1, *z.shape[1:]), generator=g) for g in gens]).to(z)
-                else:
-                    eps = torch.randn(z.shape, generator=gen).to(z)
+                eps = noise.host_draw(i, z)
                 z = w_z * z + w_x * x0 + scale * eps
             if return_all:
                 zs.append(z)
         return torch.stack(zs, dim=0) if return_all else z
-
-    def _sample_hip(self, z, n, noises, seed, verbose, use_graph, kwargs, return_all=False, seeds=None):
-        coef = self.step_table(n).to(device=z.device, dtype=torch.float32).contiguous()
-        cfg = self.w_cfg is not None and not self.training
-        if cfg:
-            assert "v_conditionings" in kwargs, "Need v_conditionings to mask out"
-        return hip_graph_sampler(self.score_model, z, coef, noises, seed, verbose, use_graph, kwargs.get("s_conditioning"),
-                                 list(kwargs.get("v_conditionings") or []), w_cfg=float(self.w_cfg) if cfg else None,
-                                 mask_fn=self.cfg_mask, return_all=return_all, seeds=seeds)
-
-
-def hip_graph_sampler(net, z, coef, noises, seed, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None,
-                      return_all=False, seeds=None):
-    """The multi-step sampling loop on the HIP backend, shared by the VDM ancestral sampler and the SFM Euler integrator: per step
-    [conditioning-table row gather, UNet forward, fused update z <- ratio * (z - cs * net_out) + scale * noise, step counter + 1],
-    captured once in a hipGraph and replayed; coef[n][4] = {ratio, cs, scale, network time} is read on the device at the row of the
-    device-side step counter.  z is updated in place and returned; return_all: the stack [n, B, ...] of z after every step instead
-    (frame vdm_model.py:429-442: ``return_all``), copied out between the replays of the same graph.
-    seeds (one int per row of z): the update draws row r's noise from seeds[r] (vdm_ancestral_step_rows) instead of one stream for the
-    whole batch from `seed`; the seed table is uploaded here, before the capture."""
-    from . import hip_ops as ops
-    from .unet_hip import hip_unet_apply
-    dev = z.device
-    n = coef.shape[0]
-    step = torch.zeros(1, dtype=torch.int32, device=dev)
-    B = z.shape[0]
-    seeds_dev = None
-    if seeds is not None:
-        assert len(seeds) == B and noises is None
-        seeds_dev = torch.tensor([int(s) for s in seeds], dtype=torch.int64, device=dev)
-    elif seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    else:
-        seed = int(seed)
-    feed = _NoiseFeed(noises, z) if noises is not None else None
-    noise_buf = feed.buf if feed is not None else None
-    cfg = w_cfg is not None
-    table_t, table_v, table, s_cond, R, W = _sampler_conditioning(net, coef[:, 3].contiguous(), B, s_cond, v_conditionings, cfg, mask_fn)
-    zz = torch.empty(R, *z.shape[1:], device=dev) if cfg else z
-
-    def one_step():
-        if table_t is not None or table_v is not None:
-            ops.cond_table_step(table_t, table_v, step, R, W, table)
-        if cfg:
-            zz[:B].copy_(z)
-            zz[B:].copy_(z)
-        eps_hat = hip_unet_apply(net, zz, s_cond, table=table).contiguous()
-        if seeds_dev is not None:                          # row-keyed noise: chain r's stream is seeds[r]'s, in any batch
-            ops.ancestral_step_rows(z, eps_hat[:B], coef, step, seeds_dev, eps_uncond=eps_hat[B:] if cfg else None,
-                                    w_cfg=w_cfg if cfg else 0.0)
-        elif cfg:                                          # blend inside K9: the guided estimate is never materialised
-            ops.ancestral_step(z, eps_hat[:B], noise_buf, coef, step, seed, eps_uncond=eps_hat[B:], w_cfg=w_cfg)
-        else:
-            ops.ancestral_step(z, eps_hat, noise_buf, coef, step, seed)
-        ops.step_inc(step)
-
-    graph = None
-    if use_graph and n > 2:
-        z_keep = z.clone()
-
-        def restore():
-            z.copy_(z_keep)
-            step.zero_()
-
-        graph = _capture_step(one_step, dev, restore, prime=None if feed is None else lambda: noise_buf.copy_(noises[0].to(z)))
-    zs = torch.empty((n,) + tuple(z.shape), dtype=z.dtype, device=dev) if return_all else None
-    for i in range(n):
-        if feed is not None:
-            feed.load(i)
-        if graph is not None:
-            graph.replay()
-        else:
-            one_step()
-        if zs is not None:
-            zs[i].copy_(z)
-        if verbose and (i % 50 == 0 or i == n - 1):
-            print(f"sampling: {i + 1}/{n}", flush=True)
-    return zs if return_all else z
-
-
-def _sampler_conditioning(net, t_norm, B, s_cond, v_conditionings, cfg, mask_fn):
-    """The conditioning of every step of a sampling loop is known up front: ONE K6 launch embeds all time values (one table row per
-    grid index), one more the vector conditionings; inside the step a single gather-add kernel (cond_table_step) builds the table from
-    a device-side row index.  cfg: guided + v-masked rows of one batch-doubled forward (VDM._cfg_pair).  Returns (table_t, table_v,
-    table [R, W], s_cond expanded to the R rows the UNet sees, R, W)."""
-    from . import hip_ops as ops
-    dev = net.flat.device
-    W = net.table_width
-    table_t = table_v = None
-    with torch.no_grad():
-        fl = net.flat.detach()
-        if net.t_conditioning:
-            table_t = ops.CondTable(net.cond_specs(t_norm, None, fl, which="t"), t_norm.shape[0], W).forward(save=False)
-        vs = [v.to(device=dev, dtype=torch.float32).expand(B, -1).contiguous() for v in v_conditionings]
-        if cfg:
-            vs = [torch.cat([v, m], dim=0).contiguous() for v, m in zip(vs, mask_fn(vs))]
-        R = 2 * B if cfg else B                            # rows the UNet sees
-        if vs:
-            table_v = ops.CondTable(net.cond_specs(None, vs, fl, which="v"), R, W).forward(save=False)
-    if s_cond is not None:                                 # one conditioning cube serves every row of the batch
-        s_cond = s_cond.to(dev).expand(B, *s_cond.shape[1:])
-        s_cond = (torch.cat([s_cond, s_cond], dim=0) if cfg else s_cond).contiguous()
-    return table_t, table_v, torch.zeros(R, W, device=dev), s_cond, R, W
-
-
-def _capture_step(one_step, dev, restore, prime=None):
-    """Warm-up of `one_step` on a side stream (packs weights, sizes the allocator; `prime` runs first on that stream), then its capture
-    in a hipGraph; `restore` puts the loop's state (z, device counters) back after each of the two."""
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        if prime is not None:
-            prime()
-        one_step()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    restore()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        one_step()
-    restore()                       # capture does not execute, but keep the state explicit
-    return graph
-
-
-class _NoiseFeed:
-    """Supplied noise fields (tests / oracle comparisons; the product path draws them in-kernel): uploaded in blocks of <= 256 MB and copied
-    device-to-device into `buf` per draw - one pageable host-to-device copy between every two graph replays was the only thing the tests
-    that intermittently took the process down (round 4) did differently from the product's sampling loop."""
-
-    def __init__(self, noises, like):
-        self.noises, self.like, self.n = noises, like, len(noises)
-        self.buf = torch.empty_like(like)
-        self.blk = max(1, min(self.n, (256 << 20) // max(1, like.numel() * like.element_size())))
-        self.first, self.block = None, None
-
-    def load(self, i):
-        first = i - i % self.blk
-        if first != self.first:
-            self.block = torch.stack([self.noises[k].to(dtype=self.like.dtype) for k in range(first, min(self.n, first + self.blk))]).to(
-                self.like.device)
-            self.first = first
-        self.buf.copy_(self.block[i - first])
-
-
-# ------------------------------------------------------------------------------------------------------------------ DDNM
-def ddnm_lengths(n_sampling_steps, l):
-    """The time-travel length of every outer step as an integer array (an int: the same for all)."""
-    import numpy as np
-    if isinstance(l, (int, np.integer)):
-        l = np.full(n_sampling_steps, int(l))
-    l = np.asarray(l)
-    if not (l.ndim == 1 and len(l) == n_sampling_steps and np.issubdtype(l.dtype, np.integer) and np.all(l >= 0)):
-        raise ValueError("l must be a non-negative integer or an integer array of length n_sampling_steps")
-    return l
-
-
-def ddnm_schedule(n_sampling_steps, l):
-    """The DDNM loop of /root/reference/src/utils.py:290-299 unrolled on the host.  Outer step i travels back L = min(l[i], i) grid
-    steps (one draw) and then evaluates the network at t = steps[k], s = steps[k+1] for k = i-L .. i (one draw each).  Returns
-    k / draw / outer: per evaluation, in order, the grid index, the number of its update draw and its outer step; L / travel_draw: per
-    outer step; n_draws (z_1 is not counted: draw d is the d+1-th field after it)."""
-    l = ddnm_lengths(n_sampling_steps, l)
-    out = {"k": [], "draw": [], "outer": [], "L": [], "travel_draw": []}
-    d = 0
-    for i in range(n_sampling_steps):
-        L = int(min(l[i], i))
-        out["L"].append(L)
-        out["travel_draw"].append(d)
-        d += 1
-        for j in range(L, -1, -1):
-            out["k"].append(i - j)
-            out["draw"].append(d)
-            out["outer"].append(i)
-            d += 1
-    out["n_draws"] = d
-    return out
-
-
-def ddnm_sample(model, y, A, AT, operator, n, l, return_all, verbose, seed, seeds, noises, use_graph, device, kwargs, stats=None):
-    """The seed- / noise-keyed DDNM sampler behind utils.get_ddnm_result's new keywords: on the HIP backend the device loop
-    hip_ddnm_sampler, on the torch backend the reference-order loop with the same arguments (noises in call order; seeds: one
-    generator per chain, manual_seed(s + 1), as VDM.sample's torch path; seed: one generator for the batch).  The batch is y's row
-    count.  stats: see utils.get_ddnm_result."""
-    B = y.shape[0]
-    cube = tuple(model.score_model.shape)
-    sch = ddnm_schedule(n, l)
-    if seeds is not None:
-        seeds = [int(s) for s in seeds]
-        if len(seeds) != B:
-            raise ValueError(f"get_ddnm_result: {len(seeds)} seeds for {B} rows of y (one seed per chain)")
-    if sum(a is not None for a in (seed, seeds, noises)) > 1:
-        raise ValueError("get_ddnm_result: seed=, seeds= and noises= cannot be combined")
-    if noises is not None and len(noises) != 1 + sch["n_draws"]:
-        raise ValueError(f"get_ddnm_result: {len(noises)} noises, the schedule draws {1 + sch['n_draws']} fields (z_1 first)")
-    if operator is not None:
-        operator.check((B,) + cube)
-        A, AT = operator.A, operator.AT
-    if A is None or AT is None:
-        raise ValueError("get_ddnm_result: give A and AT, or operator=")
-    if noises is not None:
-        z = noises[0].clone()
-    elif seeds is not None:
-        z = torch.cat([torch.randn((1,) + cube, generator=torch.Generator().manual_seed(s)) for s in seeds])
-    elif seed is not None:
-        z = torch.randn((B,) + cube, generator=torch.Generator().manual_seed(int(seed)))
-    else:
-        z = torch.randn((B,) + cube, device=device)
-    z = z.to(device=device, dtype=torch.float32).contiguous()
-    y = y.to(device)
-    with torch.no_grad():
-        if model._hip(z):
-            return hip_ddnm_sampler(model, z, y, A, AT, operator, n, sch, noises, seed, seeds, use_graph, return_all, verbose, kwargs,
-                                    stats)
-        gens = None
-        if seeds is not None:
-            gens = [torch.Generator().manual_seed(s + 1) for s in seeds]
-        elif seed is not None:
-            gens = torch.Generator().manual_seed(int(seed) + 1)
-
-        def draw(d):
-            if noises is not None:
-                return noises[d + 1].to(z)
-            if isinstance(gens, list):
-                return torch.cat([torch.randn((1,) + cube, generator=g) for g in gens]).to(z)
-            return torch.randn_like(z) if gens is None else torch.randn(z.shape, generator=gens).to(z)
-
-        steps = torch.linspace(1.0, 0.0, n + 1, device=device)
-        ATy = AT(y)
-        xs, x_r, e = [], None, 0
-        for i in range(n):
-            L = sch["L"][i]
-            z = model.sample_zt_given_zs(zs=z, t=steps[i - L], s=steps[i], noise=draw(sch["travel_draw"][i]))
-            for _ in range(L + 1):
-                k = sch["k"][e]
-                w_z, w_x, x0, scale = model.sample_zs_given_zt(zt=z, t=steps[k], s=steps[k + 1], return_ddnm=True, **kwargs)
-                x_r = ATy + x0 - AT(A(x0))
-                z = w_z * z + w_x * x_r + scale * draw(sch["draw"][e])
-                e += 1
-            if return_all:
-                xs.append(x_r)
-        return torch.stack(xs, dim=0) if return_all else x_r
-
-
-def hip_ddnm_sampler(model, z, y, A, AT, operator, n, sch, noises, seed, seeds, use_graph, return_all, verbose, kwargs, stats=None):
-    """DDNM on the HIP backend.  The captured inner step is [conditioning-table gather at k, UNet forward, DDNM kernels (+ the callables
-    AT(A(.)) of a generic operator), cursor advance]; the host loop launches the travel-back kernel and replays the step L+1 times per
-    outer step - no host synchronisation, no allocation after the capture.  All scalars come from device tables at the device cursor
-    (ops.DdnmTables); noise is supplied (`noises`, z_1 first) or drawn in the kernels, keyed by (seeds[r], draw + 1) per row, or by
-    (seed, draw + 1) over the whole batch.  A generic operator must be device-only torch ops with fixed shapes to be captured
-    (use_graph=False runs the same kernels un-captured)."""
-    from . import hip_ops as ops
-    from .unet_hip import hip_unet_apply
-    net, dev, B = model.score_model, z.device, z.shape[0]
-    coef, travel = model.ddnm_tables(n, sch["L"])
-    coef = coef.to(device=dev, dtype=torch.float32).contiguous()
-    travel = travel.to(device=dev, dtype=torch.float32).contiguous()
-    E = len(sch["k"])
-    # (one pad row: the advance after the last evaluation reads it)
-    sched = torch.tensor(list(zip(sch["k"] + sch["k"][-1:], sch["draw"] + sch["draw"][-1:])), dtype=torch.int32).to(dev)
-    seeds_dev, feed = None, None
-    if noises is not None:
-        feed = _NoiseFeed(noises, z)
-    elif seeds is not None:
-        seeds_dev = torch.tensor(seeds, dtype=torch.int64).to(dev)
-    else:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-        seeds_dev = torch.tensor([seed], dtype=torch.int64).to(dev)
-    tables = ops.DdnmTables(coef, sched, seeds_dev, batch_stream=noises is None and seeds is None)
-    noise_buf = feed.buf if feed is not None else None
-    cfg = model.w_cfg is not None and not model.training
-    w_cfg = float(model.w_cfg) if cfg else 0.0
-    if cfg:
-        assert "v_conditionings" in kwargs, "Need v_conditionings to mask out"
-    table_t, table_v, table, s_cond, R, W = _sampler_conditioning(net, coef[:, 5].contiguous(), B, kwargs.get("s_conditioning"),
-                                                                  list(kwargs.get("v_conditionings") or []), cfg, model.cfg_mask)
-    zz = torch.empty(R, *z.shape[1:], device=dev) if cfg else z
-    x_r = torch.empty_like(z)
-    kind = getattr(operator, "kind", None)
-    y = y.to(torch.float32)
-    if kind == "mask":
-        m = operator.mask.to(device=dev, dtype=torch.float32)
-        rows = slice(0, 1) if (m.dim() < z.dim() or m.shape[0] == 1) else slice(None)
-        m_dev = torch.broadcast_to(m, z.shape)[rows].contiguous()
-        y_dev = torch.broadcast_to(y, z.shape).contiguous()
-    elif kind == "blockmean":
-        y_dev = y.contiguous()
-    else:
-        aty = torch.broadcast_to(AT(y).to(torch.float32), z.shape).contiguous()
-        x0 = torch.empty_like(z)
-
-    def one_step():
-        if table_t is not None or table_v is not None:
-            ops.cond_table_step(table_t, table_v, tables.k_ptr, R, W, table)
-        if cfg:
-            zz[:B].copy_(z)
-            zz[B:].copy_(z)
-        eps_hat = hip_unet_apply(net, zz, s_cond, table=table).contiguous()
-        eh, eu = (eps_hat[:B], eps_hat[B:]) if cfg else (eps_hat, None)
-        if kind == "mask":
-            ops.ddnm_mask_step(z, eh, m_dev, y_dev, tables, noise_buf, x_r, eu, w_cfg)
-        elif kind == "blockmean":
-            ops.ddnm_blockmean_step(z, eh, y_dev, operator.factors, tables, noise_buf, x_r, eu, w_cfg)
-        else:
-            ops.ddnm_x0(z, eh, tables, x0, eu, w_cfg)
-            ops.ddnm_update(z, x0, AT(A(x0)).contiguous(), aty, tables, noise_buf, x_r)
-        tables.advance()
-
-    graph = None
-    if use_graph and E > 2:
-        z_keep = z.clone()
-
-        def restore():
-            z.copy_(z_keep)
-            tables.reset()
-
-        graph = _capture_step(one_step, dev, restore, prime=None if feed is None else lambda: noise_buf.copy_(noises[1].to(z)))
-    xs = torch.empty((n,) + tuple(z.shape), dtype=z.dtype, device=dev) if return_all else None
-    if stats is not None:
-        stats.update(evaluations=E, graph=graph is not None, allocated_before=torch.cuda.memory_allocated(dev))
-    e = 0
-    for i in range(n):
-        L = sch["L"][i]
-        if L > 0:                                          # (L == 0: a = 1, b = 0 - the draw is numbered, nothing is launched)
-            if feed is not None:
-                feed.load(sch["travel_draw"][i] + 1)
-            ops.ddnm_travel(z, tables, travel, i, sch["travel_draw"][i], noise_buf)
-        for _ in range(L + 1):
-            if feed is not None:
-                feed.load(sch["draw"][e] + 1)
-            if graph is not None:
-                graph.replay()
-            else:
-                one_step()
-            e += 1
-        if xs is not None:
-            xs[i].copy_(x_r)
-        if verbose and (i % 25 == 0 or i == n - 1):
-            print(f"ddnm {i + 1}/{n}", flush=True)
-    if stats is not None:
-        stats["allocated_after"] = torch.cuda.memory_allocated(dev)
-    return xs if return_all else x_r
 
 
 _TRAIN_GENS = {}
