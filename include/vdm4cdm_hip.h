@@ -184,7 +184,13 @@ int vdm_conv_wgrad_plan(const vdm_conv_desc* d, int want_bias, int accumulate, v
  * The input may be the channel-concatenation of two tensors (skip connection), never materialised.
  * stats[n][g] = {sum, sumsq} in fp32 (raw moments; mean/rstd are derived where consumed).
  * workspace: VDM_GN_STATS_WS_BYTES of scratch for the per-workgroup partials (two-stage, fixed-order
- * reduction: the forward pass is bit-reproducible). */
+ * reduction: the forward pass is bit-reproducible).
+ * Limits (VDM_ERR_ARG with a message, before any launch - a refused call writes nothing):
+ *  - groups <= 64, c1 + c2 <= 512, c1 + c2 divisible by groups, no group across the concat boundary;
+ *  - a source given as conv partials: at most 256 channels per group ((c1 + c2) / groups; one thread per channel folds the tiles);
+ *  - a source read in full: the pass writes n * B rows of 2 * groups floats into the workspace, B = workgroups per sample
+ *    (<= 2048 / n, a multiple of m = P / gcd(P, 256) with P = 16-byte pieces per voxel of that source, at least m); never more
+ *    than VDM_GN_STATS_WS_BYTES - a call whose n * m rows alone exceed it (n > 2048 / m with 64 groups) is refused. */
 #define VDM_GN_STATS_WS_BYTES (2048 * 2 * 64 * 4)
 /* part1 / part2 (may be NULL): per-tile channel partials of that source written by vdm_conv_fwd (tilesK tiles per sample);
  * the source's groups are then summed from them and xK is not read (xK may be NULL). */

@@ -925,18 +925,36 @@ __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ x,
     if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
 }
 
-// blocks per sample such that blocks*256 is a multiple of pieces-per-voxel (fixed piece column per thread)
+// blocks*256 must be a multiple of pieces-per-voxel (fixed piece column per thread): ppv = C/EPL is a power of two times {1,3,5},
+// so the block count is a multiple of m = ppv/gcd(ppv,256)
+static int piece_multiple(int ppv) {
+    int g = ppv, b = 256;
+    while (b) { const int t = g % b; g = b; b = t; }
+    return ppv / g;
+}
+
+// blocks per sample of the streaming kernels (gn_silu_fwd, gn_dyh, gn_bwd_apply): ~8 pieces per thread, about 2048 blocks in all,
+// rounded UP to a multiple of m (these kernels own no workspace: a few blocks over 2048 are harmless)
 static int blocks_per_sample(int64_t npieces, int ppv, int n) {
     int64_t want = (npieces + 256 * 8 - 1) / (256 * 8);          // ~8 pieces per thread
     int64_t cap = 2048 / (n > 0 ? n : 1);
     if (cap < 1) cap = 1;
     if (want > cap) want = cap;
     if (want < 1) want = 1;
-    // need (want*256) % ppv == 0 ; ppv = C/EPL is a power of two times {1,3}: round up to a multiple of m = ppv/gcd(ppv,256)
-    int g = ppv, b = 256;
-    while (b) { const int t = g % b; g = b; b = t; }
-    const int m = ppv / g;
+    const int m = piece_multiple(ppv);
     want = (want + m - 1) / m * m;
+    return (int)want;
+}
+
+// the same for the full statistics pass, whose n * blocks rows of partials must fit the workspace of vdm_gn_stats (2048 rows at 64
+// groups): where the rounding crossed the cap, back down to the last multiple of m under it - never below m itself (vdm_gn_stats
+// refuses the call whose n * m rows do not fit).  Equal to blocks_per_sample wherever that stayed within the cap (m = 1: always).
+static int stats_blocks_per_sample(int64_t npieces, int ppv, int n) {
+    int64_t want = blocks_per_sample(npieces, ppv, n);
+    const int64_t cap = 2048 / (n > 0 ? n : 1);
+    const int m = piece_multiple(ppv);
+    if (want > cap) want = cap / m * m;
+    if (want < m) want = m;
     return (int)want;
 }
 
@@ -970,6 +988,19 @@ extern "C" int vdm_gn_stats(const void* x1, int c1, const void* x2, int c2, int 
     const int cs[2] = {c1, c2};
     const float* parts[2] = {part1, part2};
     const int tiles[2] = {tiles1, tiles2};
+    // every refusal comes before the first launch: a call either runs whole or leaves stats / chsum / workspace untouched
+    for (int k = 0; k < 2; ++k) {
+        if (cs[k] == 0) continue;
+        if (parts[k]) {                                   // (tile_partials_fold<256>: one thread per channel of the group)
+            VDM_REQUIRE(gs <= 256, "gn_stats: %d channels per group from conv partials, the limit is 256", gs);
+            continue;
+        }
+        const int ppv = cs[k] / epl;
+        const int64_t rows = (int64_t)n * stats_blocks_per_sample(voxels * ppv, ppv, n);
+        VDM_REQUIRE(rows * 2 * groups * (int64_t)sizeof(float) <= (int64_t)VDM_GN_STATS_WS_BYTES,
+                    "gn_stats: %lld rows of %d partials exceed the workspace limit VDM_GN_STATS_WS_BYTES = %d bytes", (long long)rows,
+                    2 * groups, (int)VDM_GN_STATS_WS_BYTES);
+    }
     int g0 = 0;
     if (parts[0] && c2 > 0 && parts[1]) {                  // both halves of a concat come with conv partials: one launch
         hipLaunchKernelGGL(gn_stats_from_partials_kernel<256>, dim3(n * ((c1 + c2) / gs)), dim3(256), 0, s, parts[0], tiles[0], c1, gs, groups, 0, stats,
@@ -987,7 +1018,7 @@ extern "C" int vdm_gn_stats(const void* x1, int c1, const void* x2, int c2, int 
             continue;
         }
         const int ppv = cs[k] / epl;
-        const int bpn = blocks_per_sample(voxels * ppv, ppv, n);
+        const int bpn = stats_blocks_per_sample(voxels * ppv, ppv, n);
         if (dtype == VDM_F32)
             hipLaunchKernelGGL(gn_stats_kernel<float>, dim3(bpn * n), dim3(256), 0, s, (const float*)xs[k], cs[k], voxels, gs, groups, g0, workspace, bpn);
         else
