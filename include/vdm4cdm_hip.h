@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 16
+#define VDM_ABI_VERSION 17
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -375,6 +375,22 @@ int vdm_augment_batch(const vdm_augment_channel* host_channels, int n_channels, 
  * bit-exact copy.  src: [n][S][S][S] fp32, dst: [n][T][T][T] fp32 (x fastest), 1 <= T <= S <= 1024; S, T multiples of 4 and 16-byte
  * aligned pointers take the path with 16-byte loads and stores.  n == 0 is a successful no-op. */
 int vdm_downgrid_trilinear(const float* src, float* dst, int64_t n, int S, int T, void* stream);
+
+/* ---- data preparation: the moments of log10(field + alpha) over a resident slab (normalisation constants) --------------------------
+ * Replaces the arithmetic of the reference's notebook [REF scripts/calc_normalization.ipynb: data = np.load(path).astype(np.float64);
+ * data = np.log10(data + alpha); data.mean(), data.std()] with one streaming pass over device memory.  Per element
+ * v = log10((double)x + alpha) in float64; the element is valid when x is finite and x + alpha > 0, otherwise it is counted in n_bad
+ * and excluded from everything else.  out (device, 6 doubles) = {n_valid, S1, S2, min, max, n_bad}: S1 = sum(v - pivot),
+ * S2 = sum((v - pivot)^2) over the valid elements, min / max over the raw fp32 x of the valid elements (+inf / -inf without any), the
+ * counts exact.  With the pivot near the mean, mean = pivot + S1/N and var = S2/N - (S1/N)^2 lose nothing to cancellation; records of
+ * different slabs computed with the same pivot add.  x: n fp32 values on the device, any n in 0..2^40 and any (4-byte) alignment;
+ * workspace: VDM_LOG_MOMENTS_WS doubles on the device, overwritten.  Two launches (per-workgroup records, then one workgroup adds them
+ * in a fixed order), no atomics, a grid that depends on n alone: the same values give the same bits on every call, every device and
+ * every pointer alignment.  n == 0 writes the empty record {0, 0, 0, +inf, -inf, 0}.  VDM_ERR_ARG before any launch: NULL x / out /
+ * workspace, n < 0 (or above 2^40), a non-finite alpha or pivot. */
+#define VDM_LOG_MOMENTS_OUT 6                /* doubles */
+#define VDM_LOG_MOMENTS_WS 12288             /* doubles of workspace: 2048 workgroup records of VDM_LOG_MOMENTS_OUT */
+int vdm_log_moments(const float* x, int64_t n, double alpha, double pivot, double* out, double* workspace, void* stream);
 
 /* ---- attention block of the mid level (CUNet(mid_attn=True, n_attention_heads)) [REF trainSFM_c_uc_from_field_name.py:61,104-118;
  * NB blocks.py:169-170 `x = self.attention_blocks[i](x)`] ---------------------------------------------------------------------

@@ -76,10 +76,10 @@ class DdnmTables(C.Structure):
 
 
 PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
-_p, _i, _i64, _u64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
+_p, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _T = C.POINTER(DdnmTables)
-ABI_VERSION = 16                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 17                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -124,6 +124,7 @@ SIGNATURES = {
     "vdm_cond_input_grad": (_i, [C.POINTER(CondMlp), _i, _i, _i, _p, _p, C.POINTER(_p), _p]),
     "vdm_augment_batch": (_i, [C.POINTER(AugmentChannel), _i, _i, _i, C.POINTER(AugmentSample), _i, _p]),
     "vdm_downgrid_trilinear": (_i, [_p, _p, _i64, _i, _i, _p]),
+    "vdm_log_moments": (_i, [_p, _i64, _d, _d, _p, _p, _p]),
     "vdm_attn_split_heads": (_i, [_p, _i64, _i64, _i, _i64, _i, _i, _i, _p, _p, _p]),
     "vdm_attn_fwd": (_i, [_p, _p, _p, _i, _i64, _i, _i, _i, _f, _p, _p, _p]),
     "vdm_attn_rowdot": (_i, [_p, _p, _i, _i64, _i, _i, _i, _p, _p]),

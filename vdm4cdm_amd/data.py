@@ -133,6 +133,9 @@ NORMALIZATIONS = {"Mcdm": (10.019186475678042, 0.5520203178284999), "Mstar": (0.
 DATA_ROOT_ENV = "VDM4CDM_DATA_ROOT"
 # "1": a missing 3D_grids_<S> set is derived in HBM from the 256^3 stack (trilinear, as make_down_grids writes it) instead of failing
 DOWNGRID_ENV = "VDM4CDM_DOWNGRID"
+# a JSON file in the reference's flat schema {"<field>_m": mean, "<field>_s": std} (calc_normalization.py writes it): the constants of the
+# fields it names replace / extend NORMALIZATIONS in every AstroDataModule
+NORMALIZATIONS_ENV = "VDM4CDM_NORMALIZATIONS"
 
 
 def grid_size(dataset_name):
@@ -167,6 +170,36 @@ def _slab_sims(f):
     return max(1, (1 << 30) // max(1, f[0].nbytes))
 
 
+def load_normalizations(path):
+    """{field: (mean, std)} of a normalisation file in the reference's flat schema {"<field>_m": ..., "<field>_s": ...}
+    (the reference's src/dataset/normalizations_3d.json).  ValueError for a file that cannot be read, is not a flat object of numbers,
+    names one of a field's two constants without the other, or holds a non-finite value or a std <= 0."""
+    import json
+    try:
+        with open(path) as fh:
+            raw = json.load(fh)
+    except (OSError, ValueError) as e:
+        raise ValueError(f"normalisation file {path!r} cannot be read: {e}") from None
+    if not isinstance(raw, dict):
+        raise ValueError(f"normalisation file {path!r} holds a {type(raw).__name__}, not a flat object {{\"<field>_m\": mean, \"<field>_s\": std}}")
+    out = {}
+    for key, v in raw.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"normalisation file {path!r}: {key!r} is {v!r}, not a number (the file is a flat object of numbers)")
+        if key[-2:] not in ("_m", "_s") or len(key) < 3:
+            raise ValueError(f"normalisation file {path!r}: key {key!r} is neither \"<field>_m\" nor \"<field>_s\"")
+        if not math.isfinite(v):
+            raise ValueError(f"normalisation file {path!r}: {key!r} = {v!r} is not finite")
+        out.setdefault(key[:-2], {})[key[-1]] = float(v)
+    for field, c in out.items():
+        if len(c) != 2:
+            have, miss = ("_m", "_s") if "m" in c else ("_s", "_m")
+            raise ValueError(f"normalisation file {path!r} names {field + have!r} without {field + miss!r}")
+        if c["s"] <= 0:
+            raise ValueError(f"normalisation file {path!r}: {field + '_s'!r} = {c['s']!r} must be positive")
+    return {field: (c["m"], c["s"]) for field, c in out.items()}
+
+
 def params_path(root, suite_name, set_name):
     """.../Camels/params_new/params_{set}_{suite}.txt (/root/reference/src/dataset/CAMELS_3D_dataset.py:123)."""
     return os.path.join(root, "params_new", f"params_{set_name}_{suite_name}.txt")
@@ -196,8 +229,20 @@ class AstroDataModule:
         self.return_func = return_func if return_func is not None else default_return_func
         self.device = device
         self.alphas = [ALPHAS[c] for c in self.channel_names]
-        self.means = [NORMALIZATIONS[c][0] for c in self.channel_names]
-        self.stds = [NORMALIZATIONS[c][1] for c in self.channel_names]
+        norm_file = os.environ.get(NORMALIZATIONS_ENV)
+        from_file = load_normalizations(norm_file) if norm_file else {}
+        self._norm_from_file = [c in from_file for c in self.channel_names]
+        for c in self.channel_names:
+            if c in from_file:
+                print(f"[data] {c}: normalisation constants mean = {from_file[c][0]!r}, std = {from_file[c][1]!r} from {norm_file} "
+                      f"(${NORMALIZATIONS_ENV})", flush=True)
+            elif c not in NORMALIZATIONS:
+                raise KeyError(f"no normalisation constants for field {c!r}: the built-in table has {sorted(NORMALIZATIONS)}"
+                               + (f" and {norm_file} has {sorted(from_file)}" if norm_file else "")
+                               + f"; derive them once with `python calc_normalization.py {c}` and point ${NORMALIZATIONS_ENV} at the file it writes")
+        consts = [from_file.get(c) or NORMALIZATIONS[c] for c in self.channel_names]
+        self.means = [m for m, _ in consts]
+        self.stds = [s for _, s in consts]
         root = data_root or os.environ.get(DATA_ROOT_ENV)
         assert root, f"AstroDataModule needs the CAMELS directory (data_root= or ${DATA_ROOT_ENV})"
         sel = selection
@@ -371,12 +416,23 @@ class AstroDataModule:
         current state of every augmentation generator of this rank (train and eval; they draw lazily, batch by batch).  The position
         inside the epoch is the trainer's `batches_into_epoch`."""
         st = self._gen.get_state() if self._epoch_gen_state is None else self._epoch_gen_state
-        return {"kind": type(self).__name__, "seed": self._seed, "nsamples": int(self.nsamples), "batch_size": int(self.batch_size),
-                "crop": int(self.crop), "stage": self.stage, "epoch_gen_state": st.clone(),
-                "aug_generators": {f"{k}:{r}": g.get_state() for (k, r), g in self._aug_gens.items()}}
+        sd = {"kind": type(self).__name__, "seed": self._seed, "nsamples": int(self.nsamples), "batch_size": int(self.batch_size),
+              "crop": int(self.crop), "stage": self.stage, "epoch_gen_state": st.clone(),
+              "aug_generators": {f"{k}:{r}": g.get_state() for (k, r), g in self._aug_gens.items()}}
+        if any(self._norm_from_file):                            # constants of a file ($VDM4CDM_NORMALIZATIONS): a resume must find the same
+            sd["norm"] = self._norm_state()
+        return sd
+
+    def _norm_state(self):
+        return [[float(a), float(m), float(s)] for a, m, s in zip(self.alphas, self.means, self.stds)]
 
     def load_state_dict(self, state):
-        _check_same_module(self.state_dict(), state, skip=("epoch_gen_state", "aug_generators"))
+        mine = self.state_dict()
+        if isinstance(state, dict) and "norm" in state:          # compared whenever the saved run recorded them; a state without the
+            mine["norm"] = self._norm_state()                    # key (every default run) is accepted as it always was
+        else:
+            mine.pop("norm", None)
+        _check_same_module(mine, state, skip=("epoch_gen_state", "aug_generators"))
         self._gen.set_state(state["epoch_gen_state"])
         self._epoch_gen_state = state["epoch_gen_state"].clone()
         for key, st in state["aug_generators"].items():
@@ -507,6 +563,145 @@ def make_down_grids(root, nside, fields=("Mcdm", "Mstar"), sets=("LH", "CV", "1P
         report.append({"path": dst, "status": "written", "shape": shape, "seconds": sec})
         if verbose:
             print(f"[make_down_grids] {src} -> {dst} {shape}: " + ", ".join(f"{k} {v:.2f} s" for k, v in sec.items()), flush=True)
+    return report
+
+
+def merge_log_moments(records, pivot):
+    """(n, mean, std, min, max, n_bad) of log10(field + alpha) from the per-slab records of ``hip_ops.log_moments`` taken with ONE
+    `pivot`: the shifted sums add (math.fsum: exactly rounded), mean = pivot + S1/N, std = sqrt(max(S2/N - (S1/N)^2, 0)) - the
+    population std (ddof = 0) that np.std gives in the reference's notebook.  Pure Python float64.  Without a valid element mean and
+    std are NaN."""
+    records = list(records)
+    n = sum(int(r["n_valid"]) for r in records)
+    n_bad = sum(int(r["n_bad"]) for r in records)
+    lo = min([float(r["min"]) for r in records], default=math.inf)
+    hi = max([float(r["max"]) for r in records], default=-math.inf)
+    if n == 0:
+        return 0, math.nan, math.nan, lo, hi, n_bad
+    m1 = math.fsum(float(r["S1"]) for r in records) / n
+    m2 = math.fsum(float(r["S2"]) for r in records) / n
+    return n, float(pivot) + m1, math.sqrt(max(m2 - m1 * m1, 0.0)), lo, hi, n_bad
+
+
+def _normalization_source(root, field, suite, set_name, z, nside, alpha):
+    """(path, memory-mapped stack, alpha) of one field_normalization call, or ValueError - everything that can be refused without a GPU."""
+    if not root:
+        raise ValueError(f"field_normalization needs the CAMELS directory (root= or ${DATA_ROOT_ENV})")
+    if alpha is None:
+        if field not in ALPHAS:
+            raise ValueError(f"field_normalization: no alpha of log10(field + alpha) is known for field {field!r} (known: "
+                             f"{sorted(ALPHAS)}): give one (alpha= / --alpha)")
+        alpha = ALPHAS[field]
+    alpha = float(alpha)
+    if not math.isfinite(alpha):
+        raise ValueError(f"field_normalization: alpha = {alpha!r} is not finite")
+    if isinstance(nside, bool) or not isinstance(nside, (int, np.integer)) or nside < 1:
+        raise ValueError(f"field_normalization: nside = {nside!r} must be a positive integer")
+    path = field_path(root, "CMD" if nside == 256 else f"CMD_{nside}", suite, set_name, z, field)
+    if not os.path.exists(path):
+        raise ValueError(f"field_normalization: the stack {path} does not exist")
+    f = np.load(path, mmap_mode="r")
+    if f.ndim != 4 or f.shape[1:] != (f.shape[-1],) * 3 or f.size == 0:
+        raise ValueError(f"field_normalization: {path} has shape {f.shape}, not a stack of cubes (n, S, S, S)")
+    return path, f, alpha
+
+
+def field_normalization(root, field, suite="Astrid", set_name="LH", z="z_0.0", nside=256, alpha=None, slab_sims=None, device=None):
+    """The normalisation constants of one field - mean and population std of log10(field + alpha) in float64 over the whole stack
+    ``field_path(root, ...)`` - as the reference's scripts/calc_normalization.ipynb computes them on the host
+    (np.log10(stack.astype(np.float64) + alpha), .mean(), .std()), in one streaming pass on the device: the memory-mapped stack is
+    uploaded in slabs of whole simulations (`slab_sims`, default at most 1 GiB as in the training module), every slab is one
+    ``vdm_log_moments`` call with the same pivot (log10(first element + alpha)), and the records are merged once
+    (``merge_log_moments``).  `alpha` defaults to ALPHAS[field].
+
+    ValueError before any GPU work: no root, a missing stack, a stack that is not (n, S, S, S), no alpha for the field.  ValueError
+    after the pass: elements that are not finite or have field + alpha <= 0 (the reference's constants would be NaN there), or std == 0.
+    Returns {"field", "path", "mean", "std", "alpha", "n", "min", "max", "pivot", "seconds": {"read", "h2d", "kernel"}}."""
+    import time
+    path, f, alpha = _normalization_source(root, field, suite, set_name, z, nside, alpha)
+    step = _slab_sims(f) if slab_sims is None else int(slab_sims)
+    if step < 1:
+        raise ValueError(f"field_normalization: slab_sims = {slab_sims!r} must be at least 1")
+    first = float(np.float32(f[0, 0, 0, 0])) + alpha
+    pivot = math.log10(first) if math.isfinite(first) and first > 0 else 0.0
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise RuntimeError("field_normalization runs a HIP kernel: device must be a GPU (there is no CPU path)")
+    from . import hip_ops as ops
+    sec = dict.fromkeys(("read", "h2d", "kernel"), 0.0)
+
+    def lap(key, t0):
+        torch.cuda.synchronize(dev)
+        sec[key] += time.perf_counter() - t0
+        return time.perf_counter()
+
+    records, worst = [], math.inf
+    with torch.cuda.device(dev):
+        slab = torch.empty((min(step, len(f)),) + tuple(f.shape[1:]), dtype=torch.float32, device=dev)
+        for i in range(0, len(f), step):
+            k = min(step, len(f) - i)
+            t0 = time.perf_counter()
+            host = np.array(f[i:i + k], dtype=np.float32)             # (a copy: the read happens here, not in the upload)
+            t0 = lap("read", t0)
+            slab[:k].copy_(torch.from_numpy(host))
+            t0 = lap("h2d", t0)
+            records.append(ops.log_moments(slab[:k], alpha, pivot))
+            lap("kernel", t0)
+            if records[-1]["n_bad"]:
+                worst = min(worst, float(np.nanmin(host)) if not np.isnan(host).all() else math.nan)
+    n, mean, std, lo, hi, n_bad = merge_log_moments(records, pivot)
+    if n_bad:
+        raise ValueError(f"field_normalization: {n_bad} of {n + n_bad} elements of {path} are not finite or have field + alpha <= 0 "
+                         f"(smallest value seen {worst!r}, alpha = {alpha!r}): log10(field + alpha) is undefined there and the reference's "
+                         "constants would be NaN - clean the stack or give a larger alpha")
+    if not std > 0:
+        raise ValueError(f"field_normalization: log10({field} + {alpha!r}) is constant over {path} (std == 0, mean {mean!r}): it cannot "
+                         "be normalised")
+    return {"field": field, "path": path, "mean": mean, "std": std, "alpha": alpha, "n": n, "min": lo, "max": hi, "pivot": pivot,
+            "seconds": sec}
+
+
+def calc_normalizations(root, fields, suite="Astrid", set_name="LH", z="z_0.0", nside=256, alpha=None, out="normalizations_3d.json",
+                        device=None, verbose=True):
+    """``field_normalization`` for every field of `fields`, merged into the JSON file `out` in the reference's flat schema
+    {"<field>_m": mean, "<field>_s": std} (full float64 repr): entries of other fields are kept, the named fields are replaced.  The
+    file is rewritten after every field through a temporary file and os.replace, so an interrupted or failing run leaves the last
+    complete file.  Every source and the existing `out` are checked before any GPU work.  Returns the list of field records; a field
+    with built-in constants also reports how far the new ones are from them ("builtin", printed, never asserted)."""
+    import json
+    fields = list(fields)
+    if not fields:
+        raise ValueError("calc_normalizations: no field given")
+    for c in fields:
+        _normalization_source(root, c, suite, set_name, z, nside, alpha)
+    if os.path.exists(out):
+        load_normalizations(out)                                # (a file this tool could not have written is not overwritten)
+    report = []
+    for c in fields:
+        rec = field_normalization(root, c, suite=suite, set_name=set_name, z=z, nside=nside, alpha=alpha, device=device)
+        merged = {}
+        if os.path.exists(out):
+            with open(out) as fh:
+                merged = json.load(fh)
+        merged[f"{c}_m"], merged[f"{c}_s"] = rec["mean"], rec["std"]
+        tmp = os.path.join(os.path.dirname(os.path.abspath(out)), f".{os.path.basename(out)}.tmp{os.getpid()}")
+        try:
+            with open(tmp, "w") as fh:
+                json.dump(merged, fh, indent=2)
+                fh.write("\n")
+            os.replace(tmp, out)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        line = (f"[calc_normalization] {c}: mean = {rec['mean']!r}, std = {rec['std']!r} (alpha {rec['alpha']:g}, n = {rec['n']}, min "
+                f"{rec['min']:g}, max {rec['max']:g}; " + ", ".join(f"{k} {v:.2f} s" for k, v in rec["seconds"].items()) + f") -> {out}")
+        if c in NORMALIZATIONS:
+            m0, s0 = NORMALIZATIONS[c]
+            rec["builtin"] = {"mean": m0, "std": s0, "d_mean": rec["mean"] - m0, "d_std": rec["std"] - s0}
+            line += f"; built-in ({m0!r}, {s0!r}): mean {rec['mean'] - m0:+.3e}, std {rec['std'] - s0:+.3e}"
+        if verbose:
+            print(line, flush=True)
+        report.append(rec)
     return report
 
 

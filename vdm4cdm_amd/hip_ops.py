@@ -680,6 +680,25 @@ def downgrid_trilinear(src, T, out=None):
     return out
 
 
+LOG_MOMENTS_OUT, LOG_MOMENTS_WS = 6, 12288                  # VDM_LOG_MOMENTS_OUT / _WS (doubles)
+
+
+def log_moments(x, alpha, pivot):
+    """Moments of v = log10(x + alpha) in float64 over a contiguous fp32 tensor on the GPU (vdm_log_moments): a dict of Python numbers
+    {"n_valid", "S1" = sum(v - pivot), "S2" = sum((v - pivot)^2), "min", "max" (of the raw x), "n_bad"} over the valid elements (x finite
+    and x + alpha > 0; the others are only counted, in n_bad).  Synchronises - a tool path (data.field_normalization), not the
+    training path; records of several slabs taken with one pivot are merged by data.merge_log_moments."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(), "x must be a contiguous fp32 tensor on the GPU"
+    n = x.numel()
+    with torch.cuda.device(x.device):
+        buf = torch.empty(LOG_MOMENTS_OUT + LOG_MOMENTS_WS, dtype=torch.float64, device=x.device)
+        src = x if n else buf                               # (an empty tensor has no storage to point at; nothing is read)
+        check(_lib.lib().vdm_log_moments(_p(src), n, float(alpha), float(pivot), _p(buf), _p(buf[LOG_MOMENTS_OUT:]), _s()),
+              "vdm_log_moments")
+        r = buf[:LOG_MOMENTS_OUT].tolist()
+    return {"n_valid": int(r[0]), "S1": r[1], "S2": r[2], "min": r[3], "max": r[4], "n_bad": int(r[5])}
+
+
 def channel_sums(x, out):
     """out[c] (fp32 view) = sum over all leading dims of x[..., c]."""
     _contig(x, out)
