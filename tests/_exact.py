@@ -1,4 +1,5 @@
-"""Helpers of the exact-integer kernel checks (tests/test_input_grad_kernels_gpu.py, tests/test_groupnorm_kernels_gpu.py): operands
+"""Helpers of the exact-integer kernel checks (tests/test_input_grad_kernels_gpu.py, tests/test_groupnorm_kernels_gpu.py,
+tests/test_wgrad_kernels_gpu.py): operands
 that are small integers held as floats make every product and every partial sum an integer below 2^24, so fp32 addition is exact in
 any order and a kernel must give the bits of the same sum computed in int64 / float64 on the CPU."""
 import torch
@@ -12,6 +13,15 @@ def ints(shape, seed, terms):
     assert 4 * terms < 2 ** 24, f"exact-integer check: 4 x {terms} terms reaches 2^24, fp32 sums are no longer exact"
     g = torch.Generator().manual_seed(seed)
     return torch.randint(-2, 3, shape, generator=g, dtype=torch.int8).float()
+
+
+def ints_biased(shape, seed, terms):
+    """Uniform integers in {0..3} as fp32: every product is >= 0, so a sum of `terms` products grows to about 2.25 * terms (signed
+    data stays near sqrt(terms)) and an accumulator, LDS fold or slab kept in less than fp32 can no longer hold it exactly.
+    9 * terms must stay below 2^24."""
+    assert 9 * terms < 2 ** 24, f"exact-integer check: 9 x {terms} terms reaches 2^24, fp32 sums are no longer exact"
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 4, shape, generator=g, dtype=torch.int8).float()
 
 
 def assert_same_bits(got, ref, what):

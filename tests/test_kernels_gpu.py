@@ -1027,6 +1027,7 @@ def test_wgrad_plan_workspace_exact(case):
     conv.wgrad(xd, dd, dw_ref, db_ref, accumulate=acc)
     assert not torch.isnan(dw_ref).any()
     ws = torch.full((need + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    ws[:need] = 0xFF                                    # every float of the workspace a NaN: a slot read but never written shows
     ptr = lambda t: None if t is None else t.data_ptr()
     stream = torch.cuda.current_stream().cuda_stream
     dw, db = fresh()
