@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 17
+#define VDM_ABI_VERSION 18
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -343,6 +343,26 @@ int vdm_conv_in_dgrad(const void* dh, int n, int d, int h, int w, int c, int dty
                       float* dz, float* ds, void* stream);
 int vdm_schedule_grad_sums(const float* dz, const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps,
                            const int32_t* seed_step, int n, int64_t per, float* sums, float* workspace, void* stream);
+
+/* ---- up to three conditioning fields (ABI v18) [CUNet(s_conditioning_channels = k), k in 1..3: conv_in has cin = 1 + k <= 4 input
+ * channels, NB networks.py:259-265 cat([x, s_conditioning], dim=1)] -------------------------------------------------------------------
+ * The conditioning tensor is NCDHW fp32, cond[n][k][per] (per = d h w voxels, per % 4 == 0).  conv_in's packed NDHWC input stays ONE
+ * 16-byte piece per voxel in both storage types: {z, c_0 .. c_{k-1}, 0 ...} (4 fp32 or 8 bf16 elements), rounded like vdm_pack_input.
+ * The entries above keep their contracts (vdm_pack_input / vdm_diffuse_pack: one conditioning field, vdm_conv_in_dgrad: cin <= 2);
+ * for k = 1 the entries below give the same bits.  Every argument error (NULL pointer, k outside 1..3, cin outside 1..4, n_ds neither
+ * 0 nor cin - 1, ds NULL with n_ds > 0, per % 4 != 0, bad dtype / pad_mode, misalignment) returns VDM_ERR_ARG before any launch.
+ *   vdm_pack_fields: out[n][voxel][16 B] from z [n][per] and cond (the sampler's step).  z, cond, out 16-byte aligned.
+ *   vdm_diffuse_pack_fields: vdm_diffuse_pack for k planes - the same Philox counters (seed mixed with *seed_step, stream id, element
+ *     group), so z_t (may be NULL) and channel 0 of `packed` carry the bits vdm_diffuse_pack gives for the same arguments.
+ *   vdm_conv_in_dgrad_fields: K1t with conv_in's fp32 master weight [27][c][cin], cin in 1..4: dz [n][d][h][w] and, with
+ *     n_ds == cin - 1, the conditioning gradients ds [n][n_ds][d][h][w]; n_ds == 0: dz alone (ds is not touched).  Fixed summation
+ *     order (bit-reproducible); dz does not depend on n_ds. */
+int vdm_pack_fields(const float* z, const float* cond, int k, int n, int64_t per, int dtype, void* out, void* stream);
+int vdm_diffuse_pack_fields(const float* x, const float* cond, int k, const float* eps, uint64_t seed, uint64_t stream_id,
+                            const int32_t* seed_step, const float* alpha, const float* sigma, int n, int64_t per, int dtype, float* z_t,
+                            void* packed, void* stream);
+int vdm_conv_in_dgrad_fields(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
+                             float* dz, float* ds, int n_ds, void* stream);
 
 /* ---- data path: crop + log-normalise + flip + permute on the device -----------------------------
  * Replaces the per-sample CPU DataLoader work of [REF src/dataset/CAMELS_3D_dataset.py:53-73] (AstroDataset.__getitem__) and

@@ -99,18 +99,19 @@ def main(argv=None, configs_path=None):
         print("Processing", fol, flush=True)
         config["data_params"].update(set_name=key.split("_")[0], stage="test", batch_size=1)
         dm = utils.get_datamodule(config)
+        xi = len(utils.config_fields(config)[0])      # the target's channel index; the conditioning images show the first field (0)
         ss, images = {}, {}
 
         def ground_truth(batch, tag):
-            x = dm.unnorm_func(batch["x"].to(device), 1)
-            c = dm.unnorm_func(batch["conditioning"].to(device), 0)
+            x = dm.unnorm_func(batch["x"].to(device), xi)
+            c = dm.unnorm_func(batch["conditioning"][:, :1].to(device), 0)
             ss[f"Mcdm_GT_{tag}"] = get_stats(x, resol)
             _images(images, f"Mcdm_GT_{tag}", x, half, quarter)
             _images(images, f"cond_GT_{tag}", c, half, quarter)
 
         def generated(data, tag_of):
             for j in range(data.shape[0]):
-                x = dm.unnorm_func(torch.as_tensor(data[[j]]).to(device), 1)
+                x = dm.unnorm_func(torch.as_tensor(data[[j]]).to(device), xi)
                 ss[f"Mcdm_{tag_of(j)}"] = get_stats(x, resol)
                 _images(images, f"Mcdm_{tag_of(j)}", x, half, quarter)
 
@@ -122,7 +123,7 @@ def main(argv=None, configs_path=None):
                     break
             data = np.load(os.path.join(fol, "gen_0.npy"))
             generated(data, lambda j: f"0_{j}")
-            x_all = dm.unnorm_func(torch.as_tensor(data).to(device), 1)
+            x_all = dm.unnorm_func(torch.as_tensor(data).to(device), xi)
             results["post_means"], results["post_stds"] = x_all.mean(0, keepdim=True), x_all.std(0, keepdim=True)
         elif key == "CV_12_12":
             for i_batch, batch in enumerate(dm.test_dataloader()):

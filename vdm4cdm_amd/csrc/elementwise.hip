@@ -661,6 +661,109 @@ __global__ void __launch_bounds__(256) diffuse_pack_kernel(const float* __restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K conditioning fields (ABI v18): conv_in's packed input {z, c_0 .. c_{K-1}, 0 ...} - still ONE 16-byte piece per voxel in both storage
+// types (1 + K <= 4).  cond is NCDHW [n][K][per].  Same ownership and re-deal as diffuse_pack_kernel: a thread loads float4 (4 consecutive
+// voxels) from each of the 1 + K planes, lane L of a wave stores piece 64 r + L of the wave's 256 in round r (1 KiB per store instruction).
+// ---------------------------------------------------------------------------------------------
+template <typename T, int K>
+__device__ __forceinline__ void deal_pieces(const float (&zz)[4], const float (&cc)[K][4], int lane, int64_t wave_g0, int64_t per,
+                                            T* __restrict__ packed_n) {
+    constexpr int EPL = DT<T>::EPL;
+    static_assert(1 + K <= EPL && 1 + K <= 4, "one 16-byte piece per voxel");
+    const int src0 = lane >> 2, comp = lane & 3;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int src = 16 * r + src0;
+        float zr = 0.f, cr[K];
+#pragma unroll
+        for (int f = 0; f < K; ++f) cr[f] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = __shfl(zz[k], src, 64);
+            if (k == comp) zr = a;
+#pragma unroll
+            for (int f = 0; f < K; ++f) {
+                const float b = __shfl(cc[f][k], src, 64);
+                if (k == comp) cr[f] = b;
+            }
+        }
+        const int64_t vox = 4 * wave_g0 + 64 * r + lane;            // voxel inside the sample
+        if (vox < per) {
+            Piece<T> pc;
+#pragma unroll
+            for (int j = 0; j < EPL; ++j) pc.f[j] = 0.f;
+            pc.f[0] = zr;
+#pragma unroll
+            for (int f = 0; f < K; ++f) pc.f[1 + f] = cr[f];
+            *reinterpret_cast<uint4*>(packed_n + (size_t)vox * EPL) = pc.store();
+        }
+    }
+}
+
+template <typename T, int K>
+__global__ void __launch_bounds__(256) pack_fields_kernel(const float* __restrict__ z, const float* __restrict__ cond, int64_t per,
+                                                         T* __restrict__ packed, int blocks_per_n) {
+    constexpr int EPL = DT<T>::EPL;
+    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
+    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
+    const float4* z4 = reinterpret_cast<const float4*>(z + (size_t)n * per);
+    const float4* c4 = reinterpret_cast<const float4*>(cond + (size_t)n * K * per);
+    const int lane = threadIdx.x & 63;
+    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform: the shuffles need every lane
+    for (int64_t it = 0; it < rounds; ++it) {
+        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
+        const int64_t ic = i < n4 ? i : n4 - 1;
+        const float4 zv = z4[ic];
+        const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
+        float cc[K][4];
+#pragma unroll
+        for (int f = 0; f < K; ++f) {
+            const float4 cv = c4[(size_t)f * n4 + ic];
+            cc[f][0] = cv.x; cc[f][1] = cv.y; cc[f][2] = cv.z; cc[f][3] = cv.w;
+        }
+        deal_pieces<T, K>(zz, cc, lane, i - lane, per, packed + (size_t)n * per * EPL);
+    }
+}
+
+// diffuse_pack_kernel for K conditioning planes: the same Philox counters and the same z_t expression, so z_t and channel 0 carry the
+// bits vdm_diffuse_pack gives for the same arguments.
+template <typename T, int K>
+__global__ void __launch_bounds__(256) diffuse_pack_fields_kernel(const float* __restrict__ x, const float* __restrict__ cond,
+                                                                 const float* __restrict__ eps, uint64_t seed0, uint64_t sid,
+                                                                 const int32_t* __restrict__ seed_step, const float* __restrict__ alpha,
+                                                                 const float* __restrict__ sigma, int64_t per, float* __restrict__ z,
+                                                                 T* __restrict__ packed, int blocks_per_n) {
+    constexpr int EPL = DT<T>::EPL;
+    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
+    const uint64_t seed = mix_seed(seed0, seed_step);
+    const float al = alpha[n], si = sigma[n];
+    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
+    const size_t base = (size_t)n * per;
+    const float4* x4 = reinterpret_cast<const float4*>(x + base);
+    const float4* c4 = reinterpret_cast<const float4*>(cond + base * K);
+    const float4* e4 = eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
+    float4* z4 = z ? reinterpret_cast<float4*>(z + base) : nullptr;
+    const int lane = threadIdx.x & 63;
+    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);
+    for (int64_t it = 0; it < rounds; ++it) {
+        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
+        const bool ok = i < n4;
+        const int64_t ic = ok ? i : n4 - 1;
+        const float4 xv = x4[ic];
+        const float4 ev = e4 ? e4[ic] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + ic));
+        const float zz[4] = {al * xv.x + si * ev.x, al * xv.y + si * ev.y, al * xv.z + si * ev.z, al * xv.w + si * ev.w};
+        float cc[K][4];
+#pragma unroll
+        for (int f = 0; f < K; ++f) {
+            const float4 cv = c4[(size_t)f * n4 + ic];
+            cc[f][0] = cv.x; cc[f][1] = cv.y; cc[f][2] = cv.z; cc[f][3] = cv.w;
+        }
+        if (z4 && ok) z4[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        deal_pieces<T, K>(zz, cc, lane, i - lane, per, packed + base * EPL);
+    }
+}
+
 // K8 with the noise fields regenerated from their Philox counters instead of read (eps / eps0 NULL): the two 4-byte-per-element
 // fields of a training step never exist in memory.  Vector form of loss_terms_kernel (4 elements per thread; per % 4 == 0).
 __global__ void __launch_bounds__(256) loss_terms_rng_kernel(const float* __restrict__ x, const float* __restrict__ eps, uint64_t seed_e0,
@@ -1171,6 +1274,62 @@ extern "C" int vdm_diffuse_pack(const float* x, const float* s_cond, const float
         hipLaunchKernelGGL(diffuse_pack_kernel<bf16_t>, dim3(bpn * n), dim3(256), 0, s, x, s_cond, eps, seed, stream_id, seed_step, alpha, sigma, per,
                            z_t, (bf16_t*)packed, bpn);
     VDM_LAUNCH_CHECK("diffuse_pack_kernel");
+    return VDM_OK;
+}
+
+template <typename T>
+static void launch_pack_fields(int k, int blocks, int bpn, hipStream_t s, const float* z, const float* cond, int64_t per, void* out) {
+    if (k == 1) hipLaunchKernelGGL((pack_fields_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
+    else if (k == 2) hipLaunchKernelGGL((pack_fields_kernel<T, 2>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
+    else hipLaunchKernelGGL((pack_fields_kernel<T, 3>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
+}
+
+extern "C" int vdm_pack_fields(const float* z, const float* cond, int k, int n, int64_t per, int dtype, void* out, void* stream) {
+    VDM_REQUIRE(z && cond && out, "pack_fields: NULL pointer (z, cond and out are required)");
+    VDM_REQUIRE(k >= 1 && k <= 3, "pack_fields: %d conditioning fields out of range (1 to 3)", k);
+    VDM_REQUIRE(n > 0 && per > 0, "pack_fields: bad sizes n=%d per=%lld", n, (long long)per);
+    VDM_REQUIRE(per % 4 == 0, "pack_fields: per=%lld must be a multiple of 4", (long long)per);
+    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "pack_fields: bad dtype %d", dtype);
+    VDM_REQUIRE((((uintptr_t)z | (uintptr_t)cond | (uintptr_t)out) & 15) == 0, "pack_fields: z, cond and out must be 16-byte aligned");
+    const int bpn = bpn_for(per / 4, n);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VDM_F32) launch_pack_fields<float>(k, bpn * n, bpn, s, z, cond, per, out);
+    else launch_pack_fields<bf16_t>(k, bpn * n, bpn, s, z, cond, per, out);
+    VDM_LAUNCH_CHECK("pack_fields_kernel");
+    return VDM_OK;
+}
+
+template <typename T>
+static void launch_diffuse_pack_fields(int k, int blocks, int bpn, hipStream_t s, const float* x, const float* cond, const float* eps,
+                                       uint64_t seed, uint64_t sid, const int32_t* seed_step, const float* alpha, const float* sigma,
+                                       int64_t per, float* z_t, void* packed) {
+    if (k == 1)
+        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
+                           z_t, (T*)packed, bpn);
+    else if (k == 2)
+        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 2>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
+                           z_t, (T*)packed, bpn);
+    else
+        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 3>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
+                           z_t, (T*)packed, bpn);
+}
+
+extern "C" int vdm_diffuse_pack_fields(const float* x, const float* cond, int k, const float* eps, uint64_t seed, uint64_t stream_id,
+                                       const int32_t* seed_step, const float* alpha, const float* sigma, int n, int64_t per, int dtype,
+                                       float* z_t, void* packed, void* stream) {
+    VDM_REQUIRE(x && cond && alpha && sigma && packed, "diffuse_pack_fields: NULL pointer (x, cond, alpha, sigma and packed are required)");
+    VDM_REQUIRE(k >= 1 && k <= 3, "diffuse_pack_fields: %d conditioning fields out of range (1 to 3)", k);
+    VDM_REQUIRE(n > 0 && per > 0, "diffuse_pack_fields: bad sizes n=%d per=%lld", n, (long long)per);
+    VDM_REQUIRE(per % 4 == 0, "diffuse_pack_fields: per=%lld must be a multiple of 4", (long long)per);
+    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "diffuse_pack_fields: bad dtype %d", dtype);
+    VDM_REQUIRE((((uintptr_t)x | (uintptr_t)cond | (uintptr_t)eps | (uintptr_t)z_t | (uintptr_t)packed) & 15) == 0 &&
+                    (((uintptr_t)alpha | (uintptr_t)sigma | (uintptr_t)seed_step) & 3) == 0,
+                "diffuse_pack_fields: x, cond, eps, z_t and packed must be 16-byte aligned, alpha / sigma / seed_step 4-byte aligned");
+    const int bpn = bpn_for(per / 4, n);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VDM_F32) launch_diffuse_pack_fields<float>(k, bpn * n, bpn, s, x, cond, eps, seed, stream_id, seed_step, alpha, sigma, per, z_t, packed);
+    else launch_diffuse_pack_fields<bf16_t>(k, bpn * n, bpn, s, x, cond, eps, seed, stream_id, seed_step, alpha, sigma, per, z_t, packed);
+    VDM_LAUNCH_CHECK("diffuse_pack_fields_kernel");
     return VDM_OK;
 }
 

@@ -45,8 +45,37 @@ def gaussian_random_field(shape, generator=None, slope=-2.0, device="cpu"):
     return (x / x.std(dim=dims, keepdim=True)).float()
 
 
+MAX_COND_FIELDS = 3          # conditioning fields the HIP CUNet takes at once (conv_in's input stays one 16-byte piece per voxel)
+
+
+def split_fields(field_in):
+    """"A", "A+B" or "A+B+C" (the <field_in> of the training scripts, `in_field_name` of a config) -> the list of conditioning field
+    names.  ValueError for an empty name, a repeated field or more than MAX_COND_FIELDS fields."""
+    names = str(field_in).split("+")
+    if any(not n.strip() for n in names):
+        raise ValueError(f"conditioning fields {field_in!r}: empty field name")
+    names = [n.strip() for n in names]
+    if len(set(names)) != len(names):
+        raise ValueError(f"conditioning fields {field_in!r}: a field is repeated")
+    if len(names) > MAX_COND_FIELDS:
+        raise ValueError(f"conditioning fields {field_in!r}: at most {MAX_COND_FIELDS} fields at once, got {len(names)}")
+    return names
+
+
+def cond_return_func(n_cond, values=True):
+    """return_func(fields, params) of a conditional model on fields = [c_0, .., c_{K-1}, x]: conditioning [B, K, ...] (the K fields
+    concatenated on the channel axis), x = the last field.  The channel axis is the fourth from the end of a 3D field: the file-backed
+    module calls this per sample ([1, D, H, W] fields), the synthetic module per batch ([B, 1, D, H, W])."""
+    def return_func(fields, params):
+        cond = fields[0] if n_cond == 1 else torch.cat(list(fields[:n_cond]), dim=-4)
+        return {"conditioning": cond, "x": fields[n_cond], "conditioning_values": [params] if values else None}
+    return return_func
+
+
 class SyntheticAstroDataModule:
-    """Same surface as the reference DataModule as far as the hot path and the scripts touch it."""
+    """Same surface as the reference DataModule as far as the hot path and the scripts touch it.  len(channel_names) - 1 conditioning
+    fields (at least one): field j is the thresholded target relu(x - (1.0 - 0.5 j)), standardised - correlated with x and with each
+    other, but distinct; fields = [c_0, .., c_{K-1}, x]."""
 
     def __init__(self, cropsize=128, batch_size=2, dim=3, n_train=950, n_val=50, n_test=12, channel_names=("Mstar", "Mcdm"),
                  conditioning=True, n_params=6, seed=1000, device="cpu", return_func=None, pool=8):
@@ -77,13 +106,16 @@ class SyntheticAstroDataModule:
         shape = (batch_size, 1) + (self.cropsize,) * self.dim
         x = gaussian_random_field(shape, generator=g)
         params = PARAM_LO + (PARAM_HI - PARAM_LO) * torch.rand(batch_size, 6, generator=g)
-        cond = None
+        cond, conds = None, [None]
         if self.conditioning:
             dims = tuple(range(2, 2 + self.dim))
-            c = torch.relu(x - 1.0)
-            c = c - c.mean(dim=dims, keepdim=True)
-            cond = c / c.std(dim=dims, keepdim=True).clamp(min=1e-6)
-        fields = [cond, x]
+            conds = []
+            for j in range(max(1, len(self.channel_names) - 1)):
+                c = torch.relu(x - (1.0 - 0.5 * j))
+                c = c - c.mean(dim=dims, keepdim=True)
+                conds.append(c / c.std(dim=dims, keepdim=True).clamp(min=1e-6))
+            cond = conds[0] if len(conds) == 1 else torch.cat(conds, dim=1)
+        fields = conds + [x]
         if self.return_func is not None:
             batch = self.return_func(fields, params[:, :self.n_params])
         else:

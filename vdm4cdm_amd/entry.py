@@ -79,15 +79,16 @@ def _resume_path(log_dir, experiment_name):
     return path
 
 
-def _figure_closure(dm, thickness, with_values):
-    """draw_figure(batch, samples) as the scripts build it (images of a projected slab, P(k), cross-correlation)."""
+def _figure_closure(dm, thickness, with_values, x_channel=1):
+    """draw_figure(batch, samples) as the scripts build it (images of a projected slab, P(k), cross-correlation).  x_channel: the
+    target's index in the data module's channel list (K with K conditioning fields); the conditioning image is the first field's."""
     from . import figures, utils
 
     def to_np(t):
         return t.detach().cpu().numpy()
 
     def x_to_im(field):
-        return to_np(dm.norm_func(dm.unnorm_func(field, 1)[0, :, :, :thickness].sum(-1), 1))
+        return to_np(dm.norm_func(dm.unnorm_func(field, x_channel)[0, :, :, :thickness].sum(-1), x_channel))
 
     def conditioning_to_im(field):
         return to_np(dm.norm_func(dm.unnorm_func(field, 0)[0, :, :, :thickness].sum(-1), 0))
@@ -110,31 +111,43 @@ def _figure_closure(dm, thickness, with_values):
     return draw_figure
 
 
+def parse_fields(field_in, field_out, multi=True):
+    """<field_in> <field_out> of a conditional training script -> (channel_names, K): field_in may name up to three conditioning fields
+    as A+B+C (channel_names = [A, B, C, out], K = 3).  A bad list is a SystemExit before any model or GPU work; multi=False (the
+    flow-matching scripts: one source field) refuses a list."""
+    from .data import split_fields
+    if not multi and "+" in field_in:
+        raise SystemExit(f"<field_in> = {field_in!r}: this script maps ONE source field to the target; several conditioning fields "
+                         "(A+B+C) are for the VDM scripts")
+    try:
+        names = split_fields(field_in)
+    except ValueError as e:
+        raise SystemExit(f"usage: <script> <field_in>[+<field_in>[+<field_in>]] <field_out> ...: {e}")
+    return names + [field_out], len(names)
+
+
 def train_vdm3d(variant, argv=None):
     from . import data, networks, vdm_model
     from .trainer import Trainer
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 3:
-        raise SystemExit("usage: <script> <field_in> <field_out> <cropsize>")
+        raise SystemExit("usage: <script> <field_in>[+<field_in>[+<field_in>]] <field_out> <cropsize>")
     field_in, field_out, cropsize = argv[0], argv[1], int(argv[2])
+    channel_names, n_cond = parse_fields(field_in, field_out)
     dataset_name, chs, n_values, val_every, name_pat, thick = VDM3D_VARIANTS[variant]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
     resume = _resume_path(log_dir, name)
     _seed_everything(42)
     batch_size = 2
-
-    def return_func(fields, params):
-        return {"conditioning": fields[0], "x": fields[1], "conditioning_values": [params] if n_values else None}
-
-    dm = data.get_dataset(dataset_name=dataset_name, suite_name="Astrid", return_func=return_func, set_name="LH", z_name="z_0.0",
-                          channel_names=[field_in, field_out], stage="fit", batch_size=batch_size, cropsize=cropsize,
-                          num_workers=16, mmap=False)
+    dm = data.get_dataset(dataset_name=dataset_name, suite_name="Astrid", return_func=data.cond_return_func(n_cond, bool(n_values)),
+                          set_name="LH", z_name="z_0.0", channel_names=channel_names, stage="fit", batch_size=batch_size,
+                          cropsize=cropsize, num_workers=16, mmap=False)
     score_model = networks.CUNet(
-        shape=(1, cropsize, cropsize, cropsize), chs=chs, s_conditioning_channels=1,
+        shape=(1, cropsize, cropsize, cropsize), chs=chs, s_conditioning_channels=n_cond,
         v_conditioning_dims=[] if n_values == 0 else [n_values], t_conditioning=True, norm_groups=8, mid_attn=False,
         dropout_prob=0.1, conv_padding_mode="circular" if cropsize == 256 else "zeros", n_attention_heads=4,
         backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
-    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, n_values > 0), gamma_max=13.3,
+    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, n_values > 0, x_channel=n_cond), gamma_max=13.3,
                              learning_rate=3.0e-4)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=val_every,
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
@@ -164,25 +177,23 @@ def train3d_c_c(variant, argv=None):
     from .trainer import Trainer
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 2:
-        raise SystemExit("usage: <script> <field_in> <field_out>")
+        raise SystemExit("usage: <script> <field_in>[+<field_in>[+<field_in>]] <field_out>")
     field_in, field_out = argv
+    channel_names, n_cond = parse_fields(field_in, field_out)
     cropsize, name_pat, thick = TRAIN3D_VARIANTS[variant]
     c = TRAIN3D_COMMON
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"), name_pat.format(i=field_in, o=field_out)
     resume = _resume_path(log_dir, name)
     _seed_everything(42)
 
-    def return_func(fields, params):
-        return {"x": fields[1], "conditioning": fields[0], "conditioning_values": [params]}
-
-    dm = data.get_dataset(dataset_name=c["dataset_name"], suite_name=c["suite_name"], return_func=return_func, set_name=c["set_name"],
-                          z_name="z_0.0", channel_names=[field_in, field_out], stage="fit", batch_size=c["batch_size"], cropsize=cropsize,
-                          num_workers=12, mmap=False)
+    dm = data.get_dataset(dataset_name=c["dataset_name"], suite_name=c["suite_name"], return_func=data.cond_return_func(n_cond),
+                          set_name=c["set_name"], z_name="z_0.0", channel_names=channel_names, stage="fit", batch_size=c["batch_size"],
+                          cropsize=cropsize, num_workers=12, mmap=False)
     score_model = networks.CUNet(
-        shape=(1, cropsize, cropsize, cropsize), chs=c["chs"], s_conditioning_channels=1, v_conditioning_dims=[c["conditioning_values"]],
+        shape=(1, cropsize, cropsize, cropsize), chs=c["chs"], s_conditioning_channels=n_cond, v_conditioning_dims=[c["conditioning_values"]],
         t_conditioning=True, norm_groups=c["norm_groups"], mid_attn=False, dropout_prob=c["dropout_prob"],
         conv_padding_mode=c["conv_padding_mode"], n_attention_heads=4, backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
-    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, True), gamma_min=c["gamma_min"],
+    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, True, x_channel=n_cond), gamma_min=c["gamma_min"],
                              gamma_max=c["gamma_max"], noise_schedule=c["noise_schedule"], learning_rate=c["learning_rate"])
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=c["val_check_interval"],
                       gradient_clip_val=c["gradient_clip_val"], every_n_train_steps=c["every_n_train_steps"],
@@ -225,6 +236,7 @@ def train_sfm3d(variant, argv=None):
     if len(argv) != 3:
         raise SystemExit("usage: <script> <field_in> <field_out> <cropsize>")
     field_in, field_out, cropsize = argv[0], argv[1], int(argv[2])
+    parse_fields(field_in, field_out, multi=False)
     dataset_name, chs, n_values, batch_size, name_pat, thick = SFM3D_VARIANTS[variant]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
     resume = _resume_path(log_dir, name)
@@ -260,6 +272,7 @@ def train_sfm_c_uc_2d(argv=None):
     if len(argv) != 2:
         raise SystemExit("usage: trainSFM_c_uc_from_field_name.py <field_in> <field_out>")
     field_in, field_out = argv
+    parse_fields(field_in, field_out, multi=False)
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-2D"), f"LH_c_uc_{field_in}_to_{field_out}"
     resume = _resume_path(log_dir, name)
     _seed_everything(42)

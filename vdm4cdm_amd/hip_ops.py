@@ -579,6 +579,24 @@ def pack_input(a, b, dtype, out=None):
     return out
 
 
+def pack_fields(z, cond, dtype, out=None):
+    """vdm_pack_fields: z [N, D, H, W] fp32 and K conditioning fields cond [N, K, D, H, W] fp32 (K in 1..3) -> conv_in's NDHWC input
+    [N, D, H, W, cpad(1 + K)] = {z, c_0 .. c_{K-1}, 0...} of `dtype`: one 16-byte piece per voxel.  The kernel owns 4 voxels per thread,
+    so a cube whose voxel count is no multiple of 4 is refused (ValueError) - the 3D training and sampling cubes are all even-sided."""
+    L = _lib.lib()
+    _contig(z, cond)
+    n, per = z.shape[0], z.numel() // z.shape[0]
+    assert z.dtype == cond.dtype == torch.float32 and cond.dim() == z.dim() + 1 and cond.shape[0] == n and tuple(cond.shape[2:]) == tuple(z.shape[1:])
+    k = cond.shape[1]
+    if per % 4:
+        raise ValueError(f"pack_fields: {per} voxels per sample is not a multiple of 4")
+    cp = cpad(1 + k, dtype)
+    if out is None:
+        out = torch.empty(tuple(z.shape) + (cp,), dtype=dtype, device=z.device)
+    check(L.vdm_pack_fields(_p(z), _p(cond), k, n, per, dt_id(dtype), _p(out), _s()), "vdm_pack_fields")
+    return out
+
+
 class CondTable:
     """K6: the conditioning MLPs and the additive injection table of all blocks (vdm_cond_table_*).
     specs: list of dicts {input: tensor ([rows] for the sinusoidal t embedding, [rows, d] for a vector), sinusoid: bool, in_dim,
@@ -784,6 +802,41 @@ def diffuse_pack(x, s_cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, 
     check(L.vdm_diffuse_pack(_p(x), _p(s_cond), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per, dt_id(dtype),
                              _p(z), _p(packed), _s()), "vdm_diffuse_pack")
     return z, packed
+
+
+def diffuse_pack_fields(x, cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False):
+    """diffuse_pack for K conditioning fields (vdm_diffuse_pack_fields): x [N, 1, D, H, W] (or [N, D, H, W]), cond [N, K, D, H, W], K in
+    1..3 -> (z_t fp32 or None, packed [N, D, H, W, cpad(1 + K)] = {z_t, c_0 .. c_{K-1}, 0...}).  The noise is keyed as in diffuse_pack:
+    z_t and channel 0 are the bits diffuse_pack gives for the same arguments."""
+    L = _lib.lib()
+    _contig(x, cond, eps, alpha, sigma)
+    n = x.shape[0]
+    per = x.numel() // n
+    sp = tuple(x.shape[2:]) if x.dim() == 5 else tuple(x.shape[1:])
+    assert x.dtype == cond.dtype == torch.float32 and cond.shape[0] == n and tuple(cond.shape[2:]) == sp
+    k = cond.shape[1]
+    if per % 4:
+        raise ValueError(f"diffuse_pack_fields: {per} voxels per sample is not a multiple of 4")
+    packed = torch.empty((n,) + sp + (cpad(1 + k, dtype),), dtype=dtype, device=x.device)
+    z = torch.empty_like(x) if want_z else None
+    check(L.vdm_diffuse_pack_fields(_p(x), _p(cond), k, _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per,
+                                    dt_id(dtype), _p(z), _p(packed), _s()), "vdm_diffuse_pack_fields")
+    return z, packed
+
+
+def conv_in_dgrad_fields(dh, weight, cin, circular, want_s):
+    """K1t for cin = 1 + K in 1..4 (vdm_conv_in_dgrad_fields): (dz [N, D, H, W], ds [N, K, D, H, W] or None) fp32 from dh (NDHWC
+    [N, D, H, W, C]) and conv_in's fp32 master weight [27, C, cin].  want_s False: dz alone (n_ds = 0)."""
+    L = _lib.lib()
+    _contig(dh, weight)
+    n, d, h, w, c = dh.shape
+    assert weight.dtype == torch.float32 and tuple(weight.shape) == (27, c, cin)
+    n_ds = cin - 1 if want_s else 0
+    dz = torch.empty((n, d, h, w), dtype=torch.float32, device=dh.device)
+    ds = torch.empty((n, n_ds, d, h, w), dtype=torch.float32, device=dh.device) if n_ds else None
+    check(L.vdm_conv_in_dgrad_fields(_p(dh), n, d, h, w, c, dt_id(dh.dtype), _lib.PAD_CIRCULAR if circular else _lib.PAD_ZEROS, _p(weight),
+                                     cin, _p(dz), _p(ds), n_ds, _s()), "vdm_conv_in_dgrad_fields")
+    return dz, ds
 
 
 def conv_in_dgrad(dh, weight, cin, circular, want_s):

@@ -356,9 +356,10 @@ class CUNet(nn.Module):
             if s_conditioning is not None and s_conditioning.shape[0] != B:     # one conditioning field for the whole batch
                 s_conditioning = s_conditioning.expand(B, *s_conditioning.shape[1:])
             return self._forward_torch(x, s_conditioning, table)
-        if self.dim != 3 or self.in_channels != 1 or self.s_conditioning_channels > 1:
-            raise NotImplementedError("the HIP backend covers the 3D, single-field configurations of the reference "
-                                      "(shape=(1,D,D,D), s_conditioning_channels<=1); use backend='torch' for 2D plumbing")
+        if self.dim != 3 or self.in_channels != 1 or self.s_conditioning_channels > 3:
+            raise NotImplementedError("the HIP backend covers the 3D configurations of the reference with one output field and up to "
+                                      "three conditioning fields (shape=(1,D,D,D), s_conditioning_channels<=3); use backend='torch' "
+                                      "for 2D plumbing, several input channels or more conditioning fields")
         if not x.is_cuda:
             raise RuntimeError("CUNet(backend='hip') needs tensors on a GPU; there is no CPU fallback "
                                "(construct with backend='torch' for the CPU plumbing config)")

@@ -411,7 +411,8 @@ class HipUNet:
 
     # ---------------------------------------------------------------------------------------
     def forward(self, flat, table, z, s_cond, train, seed, dropout_p=None, packed=None):
-        """z, s_cond: fp32 [N, D, H, W] (single channel).  Returns eps_hat fp32 [N, D, H, W].
+        """z: fp32 [N, D, H, W]; s_cond: fp32 [N, D, H, W] (one conditioning field) or [N, K, D, H, W] (K = 2, 3 fields, packed by
+        vdm_pack_fields).  Returns eps_hat fp32 [N, D, H, W].
         packed: conv_in's input {z, s_cond, 0...} already in NDHWC / compute dtype (the fused head of the training step wrote it).
         train: save the activations the backward pass needs (autograd is recording).  dropout_p: dropout probability of this
         call (None: net.dropout_prob in training mode, 0 in eval mode - the nn.Dropout / F.dropout(training=self.training)
@@ -424,9 +425,11 @@ class HipUNet:
         L = len(net.chs)
         ss = self._side_stream(flat.device)
         if packed is not None:
-            assert packed.dtype == dtype and tuple(packed.shape) == tuple(z.shape) + (ops.cpad(2, dtype),) and packed.is_contiguous(), \
+            assert packed.dtype == dtype and tuple(packed.shape) == tuple(z.shape) + (ops.cpad(max(2, self.cin0), dtype),) and packed.is_contiguous(), \
                 "packed conv_in input does not match (z, compute dtype)"
             xin = packed
+        elif self.cin0 > 2:
+            xin = ops.pack_fields(z, s_cond, dtype)
         else:
             xin = ops.pack_input(z, s_cond, dtype)
         h = self.conv_in.fwd(xin, P("conv_in.bias"), gn=FUSED_GN)
@@ -513,7 +516,9 @@ class HipUNet:
         dz = ds = None
         if dh is not None:
             ss.run(lambda: self.conv_in.wgrad(xin, dh, GP("conv_in.weight"), GP("conv_in.bias")), xin, dh)
-            if want_x:                # K1t: the transposed conv_in on the main stream, next to its weight gradient on the side stream
+            if want_x and self.cin0 > 2:      # K1t for K = 2, 3 conditioning fields: ds is [N, K, D, H, W]
+                dz, ds = ops.conv_in_dgrad_fields(dh, P("conv_in.weight"), self.cin0, self.conv_in.circular, bool(want[1]))
+            elif want_x:              # K1t: the transposed conv_in on the main stream, next to its weight gradient on the side stream
                 dz, ds = ops.conv_in_dgrad(dh, P("conv_in.weight"), self.cin0, self.conv_in.circular, bool(want[1]) and self.cin0 == 2)
         # (the K6 backward only needs dtable - complete since the last block - and writes its own slice of gflat: it runs on the main
         # stream WHILE the side stream finishes the conv_in weight gradient, instead of behind the join)
@@ -589,6 +594,7 @@ def _dist_rank():
 
 def hip_unet_apply(net, x, s_conditioning, table=None, t=None, v_conditionings=None, packed=None):
     """x: [B, 1, D, H, W] fp32 on the GPU (NCDHW API; C == 1 so NDHWC is the same memory).
+    s_conditioning: [B, K, D, H, W] with K = net.s_conditioning_channels (1 to 3), or [1, K, ...]: one conditioning cube for every row.
     table: optional precomputed conditioning table [B, table_width] (the sampler); otherwise t ([B]) / v_conditionings feed K6."""
     if net._exec is None:
         net._exec = HipUNet(net)
@@ -600,7 +606,9 @@ def hip_unet_apply(net, x, s_conditioning, table=None, t=None, v_conditionings=N
         s = s_conditioning.to(torch.float32)
         if s.shape[0] != B:                                # one conditioning cube for the whole batch
             s = s.expand(B, *s.shape[1:])
-        s = s.reshape(B, *x.shape[2:]).contiguous()
+        K = net.s_conditioning_channels
+        assert K == 1 or (s.dim() == x.dim() and s.shape[1] == K), f"s_conditioning must be [B, {K}, ...], got {tuple(s_conditioning.shape)}"
+        s = (s.reshape(B, *x.shape[2:]) if K == 1 else s).contiguous()
     vs = []
     if table is None:
         if t is not None:

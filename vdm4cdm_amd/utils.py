@@ -77,18 +77,26 @@ def get_ccs(fields1, fields2, full=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+def config_fields(config):
+    """(conditioning field names, K) of a config: `in_field_name` may be "A+B+C" (up to three fields); an explicit
+    `conditioning_channels` that disagrees with it is a ValueError."""
+    from .data import split_fields
+    names = split_fields(config.get("in_field_name", "Mstar"))
+    k = config.get("conditioning_channels")
+    if k is not None and int(k) not in (0, len(names)):          # (0: an unconditional model, whatever field the data module also loads)
+        raise ValueError(f"conditioning_channels = {k} disagrees with in_field_name = {config.get('in_field_name')!r} ({len(names)} fields)")
+    return names, (len(names) if k is None else int(k))
+
+
 def get_datamodule(config):
     assert "data_params" in config, "data_params not in config"
     dp = config["data_params"]
     from . import data
-
-    def return_func(fields, params):
-        return {"conditioning": fields[0], "x": fields[1], "conditioning_values": [params]}
-
+    names, _ = config_fields(config)
     return data.get_dataset(
-        dataset_name=dp["dataset_name"], suite_name=dp.get("suite_name", "Astrid"), return_func=return_func,
+        dataset_name=dp["dataset_name"], suite_name=dp.get("suite_name", "Astrid"), return_func=data.cond_return_func(len(names)),
         set_name=dp.get("set_name", "CV"), z_name=dp.get("z_name", "z_0.0"),
-        channel_names=[config["in_field_name"], config["out_field_name"]], stage=dp.get("stage", "test"),
+        channel_names=names + [config["out_field_name"]], stage=dp.get("stage", "test"),
         batch_size=dp.get("batch_size", 1), cropsize=config["cropsize"], num_workers=8, mmap=False)
 
 
@@ -105,7 +113,7 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
     score_model = networks.CUNet(
         shape=(1, cropsize, cropsize, cropsize),
         chs=config.get("chs", [32, 64, 128, 256]),
-        s_conditioning_channels=config.get("conditioning_channels", 1),
+        s_conditioning_channels=config_fields(config)[1],
         v_conditioning_dims=[] if n_values == 0 else [n_values],
         t_conditioning=True, norm_groups=8, mid_attn=False, dropout_prob=0.1,
         conv_padding_mode="circular" if cropsize == 256 else "zeros", n_attention_heads=4,

@@ -70,6 +70,15 @@ class _ElboFn(torch.autograd.Function):
         return g * d, None, None, None, None, None, None, None
 
 
+def _cond_fields(s_c, x, K):
+    """The K > 1 conditioning fields of a training batch as contiguous fp32 [B, K, D, H, W] on x's device."""
+    assert s_c is not None, f"s_conditioning_channels={K} needs s_conditioning"
+    s_c = s_c.to(device=x.device, dtype=torch.float32)
+    assert s_c.dim() == x.dim() and s_c.shape[1] == K and s_c.shape[2:] == x.shape[2:], \
+        f"s_conditioning must be [B, {K}, ...] on the grid of x, got {tuple(s_c.shape)}"
+    return s_c.expand(x.shape[0], *s_c.shape[1:]).contiguous()
+
+
 class _LearnedDiffuseFn(torch.autograd.Function):
     """z_t = alpha_n x + sigma_n eps of the learned schedule through the fused head (vdm_diffuse_pack: conv_in's packed input in the same
     pass; eps None: drawn in the kernel from rng = (seed, stream)).  Backward: d alpha_n = sum dz x, d sigma_n = sum dz eps (K7b, eps read
@@ -78,8 +87,9 @@ class _LearnedDiffuseFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, alpha, sigma, x, eps, rng, s_cond, dtype):
         from . import hip_ops as ops
-        z_t, xin = ops.diffuse_pack(x, s_cond, alpha.detach().contiguous(), sigma.detach().contiguous(), dtype, eps=eps, seed=rng[0],
-                                    stream_id=rng[1], want_z=True)
+        head = ops.diffuse_pack_fields if (s_cond is not None and s_cond.shape[1] > 1) else ops.diffuse_pack      # [B, K, ...], K = 2, 3
+        z_t, xin = head(x, s_cond, alpha.detach().contiguous(), sigma.detach().contiguous(), dtype, eps=eps, seed=rng[0],
+                        stream_id=rng[1], want_z=True)
         ctx.save_for_backward(x, eps)
         ctx.rng = rng
         ctx.mark_non_differentiable(xin)
@@ -234,7 +244,7 @@ class VDM(nn.Module):
             # counters.  The host draws the two seeds exactly as the unfused path does (same generator state -> same noise fields).
             sm = self.score_model
             fuse = (FUSED_HEAD and eps is None and eps0 is None and numel % 4 == 0 and (self.w_cfg is None or self.training)
-                    and x.dim() == 5 and getattr(sm, "s_conditioning_channels", 0) <= 1)
+                    and x.dim() == 5 and getattr(sm, "s_conditioning_channels", 0) <= 3)
             rng = None
             if fuse:
                 rng = ((noise_seed(), 2 * rank + 1), (noise_seed(), 2 * rank + 2))
@@ -261,10 +271,14 @@ class VDM(nn.Module):
             if fuse:
                 s_c = kwargs.get("s_conditioning") if sm.s_conditioning_channels else None
                 assert s_c is not None or not sm.s_conditioning_channels, "s_conditioning_channels=1 needs s_conditioning"
-                if s_c is not None:
-                    s_c = s_c.to(device=x.device, dtype=torch.float32).expand(x.shape).contiguous()
                 dt = torch.bfloat16 if sm.precision == "bf16" else torch.float32
-                z_t, xin = ops.diffuse_pack(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True)
+                if sm.s_conditioning_channels > 1:         # K = 2, 3 conditioning fields: the same head with K planes
+                    s_c = _cond_fields(s_c, x, sm.s_conditioning_channels)
+                    z_t, xin = ops.diffuse_pack_fields(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True)
+                else:
+                    if s_c is not None:
+                        s_c = s_c.to(device=x.device, dtype=torch.float32).expand(x.shape).contiguous()
+                    z_t, xin = ops.diffuse_pack(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True)
                 eps_hat = self.score_model(z_t, t=sc[4], _packed_input=xin, **kwargs)
             else:
                 z_t = ops.diffuse(x, eps.contiguous(), sc[1], sc[2])
@@ -320,7 +334,9 @@ class VDM(nn.Module):
         g_t = self.gamma_b + wabs * times
         t_norm = (g_t - self.gamma_min) / (self.gamma_max - self.gamma_min)
         s_c = kwargs.get("s_conditioning") if sm.s_conditioning_channels else None
-        if s_c is not None:
+        if sm.s_conditioning_channels > 1:
+            s_c = _cond_fields(s_c, x, sm.s_conditioning_channels)
+        elif s_c is not None:
             s_c = s_c.to(device=dev, dtype=torch.float32).expand(x.shape).contiguous()
         dt = torch.bfloat16 if sm.precision == "bf16" else torch.float32
         z_t, xin = _LearnedDiffuseFn.apply(self.alpha(g_t), self.sigma(g_t), x, None if eps is None else eps.contiguous(), rng_e, s_c, dt)
