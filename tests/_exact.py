@@ -1,5 +1,5 @@
 """Helpers of the exact-integer kernel checks (tests/test_input_grad_kernels_gpu.py, tests/test_groupnorm_kernels_gpu.py,
-tests/test_wgrad_kernels_gpu.py): operands
+tests/test_wgrad_kernels_gpu.py, tests/test_attention_kernels_gpu.py): operands
 that are small integers held as floats make every product and every partial sum an integer below 2^24, so fp32 addition is exact in
 any order and a kernel must give the bits of the same sum computed in int64 / float64 on the CPU."""
 import torch
@@ -34,9 +34,11 @@ def assert_same_bits(got, ref, what):
         raise AssertionError(f"{what}: {bad.shape[0]} of {got.numel()} values differ; first (index, got, ref): {first}")
 
 
-def in_sentinel(numel, shape, pad=64, value=-7777.0):
-    """A contiguous fp32 view of `shape` in the middle of a larger sentinel-filled buffer; returns (buffer, view, check)."""
-    buf = torch.full((numel + 2 * pad,), value, dtype=torch.float32, device=DEV)
+def in_sentinel(numel, shape, pad=64, value=-7777.0, dtype=torch.float32):
+    """A contiguous view of `shape` (fp32 unless `dtype` says otherwise) in the middle of a larger sentinel-filled buffer; returns
+    (buffer, view, check).  The sentinel is `value` rounded to `dtype`."""
+    value = torch.tensor(value, dtype=dtype).item()
+    buf = torch.full((numel + 2 * pad,), value, dtype=dtype, device=DEV)
     view = buf[pad:pad + numel].view(shape)
 
     def untouched():

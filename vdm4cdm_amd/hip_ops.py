@@ -763,14 +763,18 @@ def attn_fwd(q, k, vt, scale, out_shape, want_lse=True):
     return out, lse
 
 
-def attn_bwd(q, k, v, qt, kt, dout, out, lse, scale):
-    """-> dqkv [N, ..., 3 * H*hd] (the gradient of the qkv conv's output).  dout / out: [N, ..., H*hd]."""
-    _contig(q, k, v, qt, kt, dout, out, lse)
+def attn_bwd(q, k, v, qt, kt, dout, out, lse, scale, dsum=None):
+    """-> dqkv [N, ..., 3 * H*hd] (the gradient of the qkv conv's output).  dout / out: [N, ..., H*hd].  dsum: [N, H, V] fp32 used in
+    place of rowsum(dout * out) (then `out` is not read and may be None); the kernel tests supply integers there."""
+    _contig(q, k, v, qt, kt, dout, out, lse, dsum)
     N, H, V, hd = q.shape
     L = _lib.lib()
     doh, dot = attn_split_heads(dout, 0, 1, H)
-    dsum = torch.empty((N, H, V), dtype=torch.float32, device=q.device)
-    check(L.vdm_attn_rowdot(_p(dout), _p(out), N, V, H, hd, dt_id(q.dtype), _p(dsum), _s()), "vdm_attn_rowdot")
+    if dsum is None:
+        dsum = torch.empty((N, H, V), dtype=torch.float32, device=q.device)
+        check(L.vdm_attn_rowdot(_p(dout), _p(out), N, V, H, hd, dt_id(q.dtype), _p(dsum), _s()), "vdm_attn_rowdot")
+    else:
+        assert dsum.dtype == torch.float32 and tuple(dsum.shape) == (N, H, V) and dsum.device == q.device
     dqkv = torch.empty(tuple(dout.shape[:-1]) + (3 * H * hd,), dtype=q.dtype, device=q.device)
     check(L.vdm_attn_bwd(_p(q), _p(k), _p(v), _p(qt), _p(kt), _p(doh), _p(dot), _p(lse), _p(dsum), N, V, H, hd, dt_id(q.dtype), float(scale),
                          _p(dqkv), _s()), "vdm_attn_bwd")
