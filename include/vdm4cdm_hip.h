@@ -302,7 +302,10 @@ int vdm_cond_input_grad(const vdm_cond_mlp* mlps, int n, int rows, int width, co
                         float* const* host_dinputs, void* stream);
 
 /* ---- K7/K8: VDM forward diffusion + ELBO pieces [R7; D9/D10] -----------------------------------
- * z_t = alpha[n] x + sigma[n] eps  (fp32, contiguous per sample of `per` elements). */
+ * z_t = alpha[n] x + sigma[n] eps  (fp32, contiguous per sample of `per` elements).  per % 4 == 0.
+ * vdm_diffuse, vdm_diffuse_pack and vdm_loss_terms_rng read and write their fields as 16-byte vectors: every non-NULL field pointer
+ * (x, eps, z_t; x, s_cond, eps, z_t, packed; x, eps, eps_hat, eps0, d_eps_hat) must be 16-byte aligned, else VDM_ERR_ARG with a message
+ * before any launch. */
 int vdm_diffuse(const float* x, const float* eps, const float* alpha, const float* sigma, int n, int64_t per,
                 float* z_t, void* stream);
 /* sums[n][3] += {sum (eps-eps_hat)^2, sum x^2, sum (x - z0r)^2} with z0r = x + (sigma0/alpha0) eps0;

@@ -1241,6 +1241,7 @@ static int bpn_for(int64_t per, int n) {
 extern "C" int vdm_diffuse(const float* x, const float* eps, const float* alpha, const float* sigma, int n, int64_t per, float* z_t,
                            void* stream) {
     VDM_REQUIRE(x && eps && alpha && sigma && z_t && n > 0 && per > 0 && per % 4 == 0, "diffuse: bad arguments (per must be a multiple of 4)");
+    VDM_REQUIRE((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)z_t) & 15) == 0, "diffuse: x, eps and z_t must be 16-byte aligned");
     const int bpn = bpn_for(per / 4, n);
     hipLaunchKernelGGL(diffuse_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, x, eps, alpha, sigma, per, z_t, bpn);
     VDM_LAUNCH_CHECK("diffuse_kernel");
@@ -1265,6 +1266,8 @@ extern "C" int vdm_diffuse_pack(const float* x, const float* s_cond, const float
                                 void* packed, void* stream) {
     VDM_REQUIRE(x && alpha && sigma && packed && n > 0 && per > 0 && per % 4 == 0, "diffuse_pack: bad arguments (per must be a multiple of 4)");
     VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "diffuse_pack: bad dtype %d", dtype);
+    VDM_REQUIRE((((uintptr_t)x | (uintptr_t)s_cond | (uintptr_t)eps | (uintptr_t)z_t | (uintptr_t)packed) & 15) == 0,
+                "diffuse_pack: x, s_cond, eps, z_t and packed must be 16-byte aligned");
     const int bpn = bpn_for(per / 4, n);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == VDM_F32)
@@ -1338,6 +1341,8 @@ extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t see
                                   const float* coef, int n, int64_t per, float* sums, float* d_eps_hat, float* workspace, void* stream) {
     VDM_REQUIRE(x && eps_hat && coef && sums && d_eps_hat && workspace && n > 0 && per > 0 && per % 4 == 0,
                 "loss_terms_rng: bad arguments (per must be a multiple of 4)");
+    VDM_REQUIRE((((uintptr_t)x | (uintptr_t)eps | (uintptr_t)eps_hat | (uintptr_t)eps0 | (uintptr_t)d_eps_hat) & 15) == 0,
+                "loss_terms_rng: x, eps, eps_hat, eps0 and d_eps_hat must be 16-byte aligned");
     VDM_REQUIRE(n <= VDM_REDUCE_WS_ROWS, "loss_terms_rng: at most %d samples per call (got %d): the workspace holds one partial row per block",
                 VDM_REDUCE_WS_ROWS, n);
     const int bpn = bpn_for(per / 4, n);
