@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 18
+#define VDM_ABI_VERSION 19
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -126,27 +126,13 @@ int vdm_conv_dgrad_gn_tiles(const vdm_conv_desc* d);
 int vdm_conv_dgrad_gn(const vdm_conv_desc* d, const void* dout, const void* w_packed_dgrad, void* dyh, const vdm_gn_fold* fold,
                       void* stream);
 /* Which kernel family vdm_conv_fwd (dgrad = 0) / vdm_conv_dgrad (dgrad = 1) launches for this descriptor (profiling keys,
- * tests): the generic implicit-GEMM kernel or the per-parity-class kernel (up-sampling conv and its gradients, stride-2
- * dgrad).  < 0: bad descriptor. */
-#define VDM_CONV_VARIANT_GENERIC 0
-#define VDM_CONV_VARIANT_CLASS 1
+ * tests): one of the VDM_CONV_VARIANT_* values below.  < 0: bad descriptor. */
+#define VDM_CONV_VARIANT_GENERIC 0 /* the generic implicit-GEMM kernel */
+#define VDM_CONV_VARIANT_CLASS 1 /* per-parity-class kernel: up-sampling conv and its gradients, stride-2 dgrad */
 #define VDM_CONV_VARIANT_KPACK 2 /* <= 8 reduction channels (conv_in, conv_out's input gradient): 4 taps per MFMA K-step */
 #define VDM_CONV_VARIANT_SPLIT 3 /* generic kernel, half-chunk workgroups (64-cout chunks on a small grid) */
 #define VDM_CONV_VARIANT_KSPLIT 4 /* deepest level: the waves of a workgroup split the K-blocks, one weight fetch per workgroup */
 int vdm_conv_kernel_variant(const vdm_conv_desc* d, int dgrad);
-
-/* Input gradient (folded GroupNorm backward, as vdm_conv_dgrad_gn) AND weight / bias gradient (as vdm_conv_wgrad) of ONE 3x3x3 stride-1
- * conv in one launch that stages dout once (ABI v11; csrc/conv_dgw.hip) [replaces the backward of net1 / net2 of a ResNetBlock,
- * NB blocks.py:129-132, for the convs vdm_conv_dgw_supported() accepts: bf16, 32 -> 32 channels, large grids - level 0 of the 128^3
- * network].  act = the conv's saved input (the activated tensor a = drop(silu(gn(x)))); the fold's `partials` buffer holds
- * vdm_conv_dgw_tiles(d) tiles (2 x 8 x 16 voxel steps); workspace >= vdm_conv_dgw_workspace_bytes(d).  Results equal the two separate
- * entries up to fp32 summation order (the weight gradient sums the same products tile by tile in another order). */
-int vdm_conv_dgw_supported(const vdm_conv_desc* d);
-int vdm_conv_dgw_tiles(const vdm_conv_desc* d);
-size_t vdm_conv_dgw_workspace_bytes(const vdm_conv_desc* d);
-int vdm_conv_dgrad_gn_wgrad(const vdm_conv_desc* d, const void* dout, const void* w_packed_dgrad, const void* act, void* dyh,
-                            const vdm_gn_fold* fold, float* dw, float* dbias, int accumulate, void* workspace, size_t workspace_bytes,
-                            void* stream);
 
 /* dw[taps][cout][cin] (fp32) = sum over voxels; workspace holds per-workgroup partial slabs.
  * dbias (optional, ksize 3 only): dbias[cout] = sum over samples and voxels of dout (the conv bias gradient), computed

@@ -103,13 +103,6 @@ B_CASES = ["roll_half_ztile", "roll_grouped_reduce", "rows_one_ztile", "rows_256
            "s2_32_64_bf16", "s2_32_64_f32", "k1_64_32_bf16", "ups_64_32_bf16", "thin_in_1_16_5x7x33", "thin_in_2_32_16x33x40",
            "thin_out_32_4x4x70_circ"]
 
-# the fused vdm_conv_dgrad_gn_wgrad (csrc/conv_dgw.hip; 32 -> 32, bf16): name, N, grid, c1, c2, circular, accumulate.  128 tile columns
-# (vdm_conv_dgw_supported asks for half the CUs of an MI355X), odd D: 5 steps, the last one half a tile
-FusedCase = namedtuple("FusedCase", "name n grid c1 c2 circ acc")
-FUSED_CASES = [FusedCase("zeros", 2, (9, 60, 120), 32, 0, False, False), FusedCase("circular_concat", 2, (9, 60, 120), 16, 16, True, False),
-               FusedCase("zeros_acc", 2, (9, 60, 120), 32, 0, False, True)]
-FUSED_B = FUSED_CASES[0]
-
 
 def terms(c):
     """The longest sum of products a case forms: the voxels of dout."""

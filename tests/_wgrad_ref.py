@@ -4,7 +4,7 @@ ref_wgrad is the weight gradient as 27 (or 1) plain shifted matrix products in f
 ref_conv of test_kernels_gpu.py.  The bound of check B is
     |dw - ref| <= (eps_op + L * 2^-24) * abs_sum + 2^-126,       abs_sum[t] = |dout|^T |x shifted by tap t|
 with eps_op the relative error of one PRODUCT and L the number of fp32 additions one product passes through on its way into dw, both
-read off the kernels (csrc/conv_wgrad.hip, csrc/wgrad_thin.hip, csrc/conv_dgw.hip) and computed from the plan of the launch - never
+read off the kernels (csrc/conv_wgrad.hip, csrc/wgrad_thin.hip) and computed from the plan of the launch - never
 from a kernel's results."""
 import torch
 
@@ -149,19 +149,3 @@ def depth_thin(n, grid, P):
     chunks = n * D * H * cdiv(W, 32)
     L = 32 + cdiv(chunks, 4 * P) + 4 + cdiv(P, 16) + 16
     return L, L
-
-
-DGW_SLAB_FLOATS = 27 * 32 * 32 + 32 + 8      # per workgroup of conv_dgw_kernel: the slab, the bias partials, 8 floats of the diagnostic build
-
-
-def depth_fused(n, grid, workspace_bytes):
-    """conv_dgw_kernel (vdm_conv_dgrad_gn_wgrad; bf16, 32 -> 32).  P workgroups = column segments, P = workspace / slab size; a
-    weight-gradient wave owns its 7 taps and adds 8 MFMAs (16 rows, two per k-step) per 2 x 8 x 16 step, zsteps steps.  launch_dgw_reduce:
-    the slab reduces of the stand-alone kernels.  dbias: a lane adds 4 values per step, 64 lane sums folded in turn, bias reduce."""
-    D, H, W = grid
-    assert workspace_bytes % (DGW_SLAB_FLOATS * 4) == 0
-    P = workspace_bytes // (DGW_SLAB_FLOATS * 4)
-    ncols = n * cdiv(H, 8) * cdiv(W, 16)
-    assert P % ncols == 0
-    zsteps = cdiv(cdiv(D, 2), P // ncols)
-    return 32 + 8 * zsteps + _slab_reduce(P), 4 * zsteps + 64 + _bias_reduce(P)

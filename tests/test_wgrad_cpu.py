@@ -87,20 +87,6 @@ def test_case_table_covers_the_plan():
     assert {W.BY_NAME[b].kernel for b in W.B_CASES} == kernels
 
 
-def test_fused_case_plan():
-    """vdm_conv_dgw_supported / _workspace_bytes are host only (256 CUs where there is no device): the fused cases are supported there and
-    run 128 workgroups of 5 steps."""
-    from vdm4cdm_amd import _lib
-    from vdm4cdm_amd import hip_ops as ops
-    L = _lib.lib()
-    for fc in W.FUSED_CASES:
-        d = ops.Conv(32, 32, 3, circular=fc.circ).desc(fc.n, *fc.grid, torch.bfloat16)
-        assert L.vdm_conv_dgw_supported(d) == 1
-        ws = L.vdm_conv_dgw_workspace_bytes(d)
-        assert ws == 128 * R.DGW_SLAB_FLOATS * 4
-        assert R.depth_fused(fc.n, fc.grid, ws) == (32 + 40 + 36, 20 + 64 + 24)
-
-
 # ---------------------------------------------------------------------------------------------------------------- check B, CPU half
 def _b_setups():
     """(id, case, fp32 build): bf16 storage has one build, fp32 storage the split default and the exact one."""
@@ -108,8 +94,6 @@ def _b_setups():
     for name in W.B_CASES:
         c = W.BY_NAME[name]
         out += [(name, c, False)] if c.dtype == W.BF else [(name + "_split", c, False), (name + "_exact", c, True)]
-    fc = W.FUSED_B
-    out.append(("fused_" + fc.name, W.C("fused", W.BF, 32, 32, fc.n, fc.grid, "FUSED", circ=fc.circ), False))
     return out
 
 
@@ -120,13 +104,7 @@ B_SETUPS = _b_setups()
 def test_bound_admits_fp32_and_rejects_faults(setup):
     name, c, fp32_exact = setup
     bf16 = c.dtype == W.BF
-    if c.kernel == "FUSED":
-        from vdm4cdm_amd import _lib
-        from vdm4cdm_amd import hip_ops as ops
-        d = ops.Conv(32, 32, 3, circular=c.circ).desc(c.n, *c.grid, torch.bfloat16)
-        L, Lb = R.depth_fused(c.n, c.grid, _lib.lib().vdm_conv_dgw_workspace_bytes(d))
-    else:
-        L, Lb = W.depths(c, W.plan_of(c)[1], fp32_exact)
+    L, Lb = W.depths(c, W.plan_of(c)[1], fp32_exact)
     eps = R.eps_op(bf16, fp32_exact)
     x, dout = W.real_operands(c, 7)
     ref, abs_sum = R.ref_wgrad(x, dout, c.ks, c.stride, c.ups, c.circ)

@@ -1,7 +1,6 @@
-"""Kernel-level parity tests of the seven weight-gradient kernels: the six VDM_WGRAD_* kernels that plan_wgrad picks between
-(csrc/conv_common.h; csrc/conv_wgrad.hip, csrc/wgrad_thin.hip), each through vdm_conv_wgrad with a workspace of its own, and the fused
-vdm_conv_dgrad_gn_wgrad (csrc/conv_dgw.hip).  The cases are in tests/_wgrad_cases.py; tests/test_wgrad_cpu.py confirms their plans and
-the bound of check B without a device.
+"""Kernel-level parity tests of the six weight-gradient kernels, the VDM_WGRAD_* kernels that plan_wgrad picks between
+(csrc/conv_common.h; csrc/conv_wgrad.hip, csrc/wgrad_thin.hip), each through vdm_conv_wgrad with a workspace of its own.  The cases are
+in tests/_wgrad_cases.py; tests/test_wgrad_cpu.py confirms their plans and the bound of check B without a device.
 
 Two kinds of check, because they catch different faults:
   A. exact integers, no tolerance.  Operands are small integers in the storage type (exact in bf16), so every product and every partial
@@ -32,12 +31,9 @@ B, measured max over the elements of err / bound on an MI355X, default build (ke
   thin_in_1_16_5x7x33      THIN_IN     55 /  55   0.012 | 0.000
   thin_in_2_32_16x33x40    THIN_IN     86 /  86   0.001 | 0.000
   thin_out_32_4x4x70_circ  THIN_OUT    55 /   -   0.004 | -
-  fused_zeros              fused      108 / 108   0.001 | 0.000
   (the bound is a worst case over the signs of L roundings; random roundings err like sqrt(L), and the large grids average over
   10^4 - 10^5 voxels.  The emulated faults of tests/test_wgrad_cpu.py exceed the same bounds 7 to 480 times.)
 """
-import ctypes
-
 import pytest
 import torch
 
@@ -144,76 +140,6 @@ def test_wgrad_k1_refuses_a_bias_gradient():
     assert bool(torch.isnan(run.dw).all()) and bool(torch.isnan(db).all())
 
 
-# ----------------------------------------------------------------------------------------------- the fused kernel
-class FusedLaunch:
-    """vdm_conv_dgrad_gn_wgrad with a workspace of exactly vdm_conv_dgw_workspace_bytes (poisoned).  act and dout are the operands of the
-    weight gradient; the fold inputs (x, its statistics, gamma, beta, the packed weights) are any valid values: only dw / dbias are checked."""
-
-    def __init__(self, fc, act, dout):
-        _lib, ops = _mods()
-        self.fc, self.L, self.ops, self._lib = fc, _lib.lib(), ops, _lib
-        dtype = torch.bfloat16
-        n, (D, H, Wd) = fc.n, fc.grid
-        g = torch.Generator().manual_seed(21)
-        self.conv = ops.Conv(32, 32, 3, circular=fc.circ)
-        self.conv.pack((torch.randn((27, 32, 32), generator=g) / 30.0).to(DEV), dtype, need_dgrad=True)
-        self.dd = dout.to(dtype).to(DEV).contiguous()
-        self.act = act.to(dtype).to(DEV).contiguous()
-        assert self.conv.dgw_ok(self.dd, fc.c1, fc.c2)
-        self.x1 = torch.randn((n, D, H, Wd, fc.c1), generator=g).to(dtype).to(DEV)
-        self.x2 = torch.randn((n, D, H, Wd, fc.c2), generator=g).to(dtype).to(DEV) if fc.c2 else None
-        self.gamma, self.beta = (1.0 + 0.3 * torch.randn(32, generator=g)).to(DEV), (0.2 * torch.randn(32, generator=g)).to(DEV)
-        self.stats = ops.gn_stats(self.x1, self.x2, 8)
-        self.d = self.conv.desc(n, D, H, Wd, dtype)
-        self.need = self.L.vdm_conv_dgw_workspace_bytes(self.d)
-        assert self.need > 0
-        self.ws = torch.empty(self.need + GUARD, dtype=torch.uint8, device=DEV)
-        self.ws[self.need:] = 0xA5
-        self.out = torch.empty((n, D, H, Wd, 32), dtype=dtype, device=DEV)
-        self.part = torch.empty((n, self.L.vdm_conv_dgw_tiles(self.d), 32, 2), dtype=torch.float32, device=DEV)
-        self.dw_buf, self.dw, self.dw_ok = in_sentinel(27 * 32 * 32, (27, 32, 32))
-        self.db_buf, self.db, self.db_ok = in_sentinel(32, (32,))
-
-    def run(self, dw0=None, db0=None):
-        fc, p = self.fc, (lambda t: None if t is None else t.data_ptr())
-        self.ws[:self.need] = 0xFF
-        for t, t0 in ((self.dw, dw0), (self.db, db0)):
-            t.copy_(t0) if fc.acc else t.fill_(float("nan"))
-        f = self._lib.GnFold(x1=p(self.x1), x2=p(self.x2), c1=fc.c1, c2=fc.c2, groups=8, stats=p(self.stats), gamma=p(self.gamma),
-                             beta=p(self.beta), eps=self.ops.GN_EPS, inv_keep=1.0, keep_mask=None, partials=p(self.part))
-        st = self.L.vdm_conv_dgrad_gn_wgrad(self.d, p(self.dd), p(self.conv.wd), p(self.act), p(self.out), ctypes.byref(f), p(self.dw), p(self.db),
-                                            int(fc.acc), p(self.ws), self.need, torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        assert st == 0, self.L.vdm_last_error()
-        assert bool((self.ws[self.need:] == 0xA5).all()), f"{fc.name}: bytes behind the workspace were written"
-        assert self.dw_ok() and self.db_ok(), f"{fc.name}: bytes around dw / dbias were written"
-        dw, db = self.dw.cpu().clone(), self.db.cpu().clone()
-        assert not torch.isnan(dw).any() and not torch.isnan(db).any(), f"{fc.name}: NaN in the result (a slab slot read but never written)"
-        return dw, db
-
-
-@pytest.mark.parametrize("dist", list(DISTS), ids=list(DISTS))
-@pytest.mark.parametrize("fc", W.FUSED_CASES, ids=[f.name for f in W.FUSED_CASES])
-def test_fused_wgrad_exact_integers(fc, dist):
-    """The weight and bias gradient of the fused kernel against the float64 sum - until now only ever compared with another kernel."""
-    mk = DISTS[dist]
-    shape = (fc.n,) + tuple(fc.grid) + (32,)
-    nt = fc.n * fc.grid[0] * fc.grid[1] * fc.grid[2]
-    act, dout = mk(shape, 15, nt), mk(shape, 16, nt)
-    ref, _ = R.ref_wgrad(act, dout, 3, 1, 0, fc.circ)
-    bref = dout.double().reshape(-1, 32).sum(0)
-    dw0 = _start(ref.shape, 17) if fc.acc else None
-    db0 = _start(bref.shape, 18) if fc.acc else None
-    if fc.acc:
-        ref, bref = ref + dw0.double(), bref + db0.double()
-    run = FusedLaunch(fc, act, dout)
-    dw, db = run.run(dw0, db0)
-    assert_same_bits(dw, ref, f"fused {fc.name}/{dist}: dw [tap, cout, cin]")
-    assert_same_bits(db, bref, f"fused {fc.name}/{dist}: dbias")
-    dw2, db2 = run.run(dw0, db0)
-    assert torch.equal(dw, dw2) and torch.equal(db, db2), f"fused {fc.name}/{dist}: a second call gives other bits"
-
-
 # =============================================================================================== B: random reals, derived bound
 def _check_bound(name, dw, db, x, dout, ks, stride, ups, circ, L, Lb, eps):
     ref, abs_sum = R.ref_wgrad(x, dout, ks, stride, ups, circ)
@@ -238,15 +164,3 @@ def test_wgrad_random_reals_within_derived_bound(name):
     dw, db = run.run()
     L, Lb = W.depths(c, run.info, _lib.FP32_EXACT)
     _check_bound(name, dw, db, x, dout, c.ks, c.stride, c.ups, c.circ, L, Lb, R.eps_op(c.dtype == W.BF, _lib.FP32_EXACT))
-
-
-def test_fused_wgrad_random_reals_within_derived_bound():
-    fc = W.FUSED_B
-    g = torch.Generator().manual_seed(7)
-    shape = (fc.n,) + tuple(fc.grid) + (32,)
-    act = (torch.randn(shape, generator=g) + 0.3).bfloat16().float()
-    dout = torch.randn(shape, generator=g).bfloat16().float()
-    run = FusedLaunch(fc, act, dout)
-    dw, db = run.run()
-    L, Lb = R.depth_fused(fc.n, fc.grid, run.need)
-    _check_bound("fused_" + fc.name, dw, db, act, dout, 3, 1, 0, fc.circ, L, Lb, 0.0)

@@ -79,7 +79,7 @@ PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _T = C.POINTER(DdnmTables)
-ABI_VERSION = 18                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 19                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -98,10 +98,6 @@ SIGNATURES = {
     "vdm_conv_dgrad_gn_tiles": (_i, [_D]),
     "vdm_conv_dgrad_gn": (_i, [_D, _p, _p, _p, C.POINTER(GnFold), _p]),
     "vdm_conv_kernel_variant": (_i, [_D, _i]),
-    "vdm_conv_dgw_supported": (_i, [_D]),
-    "vdm_conv_dgw_tiles": (_i, [_D]),
-    "vdm_conv_dgw_workspace_bytes": (_sz, [_D]),
-    "vdm_conv_dgrad_gn_wgrad": (_i, [_D, _p, _p, _p, _p, C.POINTER(GnFold), _p, _p, _i, _p, _sz, _p]),
     "vdm_conv_wgrad_workspace_bytes": (_sz, [_D]),
     "vdm_conv_wgrad": (_i, [_D, _p, _p, _p, _p, _i, _p, _sz, _p]),
     "vdm_conv_wgrad_plan": (_i, [_D, _i, _i, C.POINTER(WgradPlanInfo)]),

@@ -32,10 +32,10 @@ static constexpr int GN_SCRATCH_BYTES = 8 * 64 * 2 * 4;      // <= 8 waves x (NC
 // ---------------------------------------------------------------------------------------------
 // geometry
 // ---------------------------------------------------------------------------------------------
-template <int KS_, int STRIDE_, int TZ_, int TY_, int NW_ = 4>
+template <int KS_, int STRIDE_, int TZ_, int TY_>
 struct Geo {
     static constexpr int KS = KS_, STRIDE = STRIDE_, TZ = TZ_, TY = TY_, TX = 16;
-    static constexpr int NW = NW_;                       // waves per workgroup (the rows of a tile are split over them)
+    static constexpr int NW = 4;                         // waves per workgroup (the rows of a tile are split over them)
     static constexpr int PAD = KS / 2;
     static constexpr int TAPS = KS * KS * KS;
     static constexpr int HZ = (TZ - 1) * STRIDE + KS, HY = (TY - 1) * STRIDE + KS, HX = (TX - 1) * STRIDE + KS;
@@ -358,7 +358,7 @@ __device__ __forceinline__ void gn_prologue_table(float* tab, const ConvArgs& a,
 template <typename T, typename G, int UPS>
 __device__ __forceinline__ void stage_halo_dma(char* lds, const T* __restrict__ x, const ConvArgs& a, int n,
                                                int oz0, int oy0, int ox0, int kb, int wave, int lane) {
-    stage_halo_dma_gen<T, G, UPS, G::NW>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
+    stage_halo_dma_gen<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -646,7 +646,7 @@ __device__ __forceinline__ void row16_sum_block(float (&v)[K]) {
 #undef VDM_DPP4
 }
 
-template <int NC, int NW = 4>
+template <int NC>
 __device__ __forceinline__ void gn_partials_reduce(float (&gs)[NC * 4], float (&gq)[NC * 4], float* sm, float* dst /* [Cout][2] of this tile */,
                                                    int cout0, int Cout, int wave, int lane, int qstride = NC * 4) {
     const int lx = lane & 15, q = lane >> 4;
@@ -664,9 +664,6 @@ __device__ __forceinline__ void gn_partials_reduce(float (&gs)[NC * 4], float (&
     if (t < NC * 16 * 2) {
         const int c = ((t >> 1) / (NC * 4)) * qstride + (t >> 1) % (NC * 4);      // lane group q owns NC*4 channels every qstride
         float tot = (sm[t] + sm[NC * 16 * 2 + t]) + (sm[2 * NC * 16 * 2 + t] + sm[3 * NC * 16 * 2 + t]);
-        if constexpr (NW == 8)
-            tot += (sm[4 * NC * 16 * 2 + t] + sm[5 * NC * 16 * 2 + t]) + (sm[6 * NC * 16 * 2 + t] + sm[7 * NC * 16 * 2 + t]);
-        static_assert(NW == 4 || NW == 8, "4 or 8 waves fold their tile sums");
         if (cout0 + c < Cout) dst[(size_t)(cout0 + c) * 2 + (t & 1)] = tot;
     }
 }
@@ -770,7 +767,7 @@ __device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[NV][NC], const 
                 for (int v = 0; v < NV; ++v) row(v, false);
             }
             if (want)
-                gn_partials_reduce<NC, G::NW>(gs, gq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout,
+                gn_partials_reduce<NC>(gs, gq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout,
                                               cwave, lane, qstride);
             return;
         }
@@ -841,7 +838,7 @@ __device__ __forceinline__ void conv_epilogue(const f32x4 (&acc)[NV][NC], const 
         }
     }
     if (a.gnp)                                            // workgroup-uniform
-        gn_partials_reduce<NC, G::NW>(gs, gq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout,
+        gn_partials_reduce<NC>(gs, gq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout,
                                       cwave, lane, qstride);
 }
 
@@ -1117,7 +1114,7 @@ __device__ __forceinline__ void conv_epilogue_gnb(const f32x4 (&acc)[NV][NC], co
             gsq[2 * j] = gq2[j].x; gsq[2 * j + 1] = gq2[j].y;
         }
     }
-    gn_partials_reduce<NC, G::NW>(gsum, gsq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout, cwave,
+    gn_partials_reduce<NC>(gsum, gsq, gn_sm, a.gnp + ((size_t)n * (a.ntz * a.nty * a.ntx) + tile) * a.Cout * 2, cout0, a.Cout, cwave,
                                   lane, qstride);
 }
 
@@ -1150,7 +1147,7 @@ template <> struct WG<bf16_t> { static constexpr int NT = 2; };
 template <> struct WG<float> { static constexpr int NT = 1; };
 
 // ---------------------------------------------------------------------------------------------
-// weight-gradient operand staging / transposed fetch (conv_wgrad.hip, conv_dgw.hip)
+// weight-gradient operand staging / transposed fetch (conv_wgrad.hip)
 // ---------------------------------------------------------------------------------------------
 // (row-wise like stage_halo_dma_rows: the row (oz, oy) is wave-uniform - scalar validity and address; per lane only the x part,
 // computed once per tile.)  sub = 1: the class sub-grid dOut[2c + p] of the up-sampling conv's parity class (pz, py, px).
@@ -1310,7 +1307,7 @@ struct Plan {
     int N, Dz, Dy, Dx;                           // tile index space (the coarse grid of an up-sampling conv)
     int layout, cls_kind;                        // packed weights: VDM_CONV_VARIANT_GENERIC | _CLASS (of ClsKind cls_kind) | _KPACK
     int family;                                  // kernel: VDM_CONV_VARIANT_*
-    int roll, wg8;                               // generic family, 4x8x16 tile: rolling-z kernel | eight waves (bit 0 plain, bit 1 folded GroupNorm backward)
+    int roll;                                    // generic family, 4x8x16 tile: rolling-z kernel
     int tz, ty;                                  // spatial tile (TX = 16)
     int tiles;                                   // per-sample tiles of the GroupNorm partials [n][tiles][O][2]
     size_t packed_bytes;
@@ -1356,11 +1353,6 @@ static void small_grid_tile(Plan& p) {
     const long long per_sample = (long long)p.nchunks * p.N * cdiv(p.Dx, 16);
     const long long tiles48 = per_sample * cdiv(p.Dz, 4) * cdiv(p.Dy, 8), tiles28 = per_sample * cdiv(p.Dz, 2) * cdiv(p.Dy, 8);
     p.tz = 4; p.ty = 8;
-    if (const char* f = getenv("VDM4CDM_FORCE_TZ")) {      // experiments: force the z extent of the tile (4 | 2 | 1)
-        p.tz = atoi(f);
-        if (p.tz == 1 || p.tz == 2 || p.tz == 4) return;
-        p.tz = 4;
-    }
     if (tiles48 >= 2LL * cu_count()) return;
     p.tz = 2;
     if (tiles28 >= cu_count()) return;
@@ -1372,26 +1364,17 @@ static void small_grid_tile(Plan& p) {
 // weights; bf16 3x3x3 stride 1, not the up-sampling conv)
 static bool uses_split(const Plan& p) {
     const long long wgs = (long long)p.nchunks * p.N * cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16);
-    return p.tz <= 2 && wgs < 2LL * cu_count() && p.O % 64 == 0 && getenv("VDM4CDM_NO_SPLIT") == nullptr;
+    static const bool split_on = getenv("VDM4CDM_NO_SPLIT") == nullptr;
+    return p.tz <= 2 && wgs < 2LL * cu_count() && p.O % 64 == 0 && split_on;
 }
 
 // K-split kernel of the deepest levels (conv_fwd.hip, conv_ksplit_kernel): bf16 3x3x3 stride-1 convs with >= 4 K-blocks and 64-cout
-// chunks whose grid is small enough for small_grid_tile() to leave the 4x8x16 tile.  Turns the (tz, ty) small_grid_tile chose into
-// the tile the K-split kernel uses (1 x ty x 16; a 2x8x16 choice becomes 1x8x16).  VDM4CDM_KSPLIT: 0 off, 1 (default) only
-// where the generic choice was a 1 x ty x 16 tile (level 3 of the 128^3 network), 2 also the 2x8x16 grids (level 2: measured SLOWER
-// there - 0.078 vs 0.054 ms at batch 2 - one workgroup per CU loses more than the saved weight traffic gains).
-static bool ksplit_tile(Plan& p) {
-    static const int level = getenv("VDM4CDM_KSPLIT") ? atoi(getenv("VDM4CDM_KSPLIT")) : 1;
-    if (level <= 0 || p.nkb < 4 || p.O % 64 != 0 || p.tz > 2 || (p.tz == 2 && level < 2)) return false;
-    if (p.tz == 2) { p.tz = 1; p.ty = 8; }
-    return true;
-}
-
-// stride-2 conv: output tile tz x 4 x 16.  2x4x16 needs a 5x9x33-voxel image (95 KB: ONE workgroup per CU, nothing overlaps its
-// staging); 1x4x16 needs 3x9x33 voxels (57 KB: two per CU).  VDM4CDM_S2_TZ selects (experiments).
-static int s2_tile_z() {
-    static const int v = getenv("VDM4CDM_S2_TZ") ? atoi(getenv("VDM4CDM_S2_TZ")) : 2;
-    return v == 1 ? 1 : 2;
+// chunks whose grid is small enough for small_grid_tile() to choose a 1 x ty x 16 tile (level 3 of the 128^3 network), which the
+// K-split kernel keeps.  Not the 2x8x16 grids (level 2: measured SLOWER there - 0.078 vs 0.054 ms at batch 2 - one workgroup per CU
+// loses more than the saved weight traffic gains).  VDM4CDM_KSPLIT=0 switches it off (A/B).
+static bool uses_ksplit(const Plan& p) {
+    static const bool on = getenv("VDM4CDM_KSPLIT") ? atoi(getenv("VDM4CDM_KSPLIT")) > 0 : true;
+    return on && p.nkb >= 4 && p.O % 64 == 0 && p.tz == 1;
 }
 
 // ---- class-conv tables -----------------------------------------------------------------------
@@ -1440,6 +1423,8 @@ static void build_cls(int kind, ClsTable& tab, ClsMasks& masks) {
     }
 }
 
+static bool kpack_enabled() { static const bool on = getenv("VDM4CDM_NO_KPACK") == nullptr; return on; }
+
 static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed validate()
     Plan p{};
     p.taps = d->ksize * d->ksize * d->ksize;
@@ -1460,24 +1445,21 @@ static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed val
         p.cls_kind = d->upsample ? (dgrad ? CLS_UP_DGRAD : CLS_UP_FWD) : CLS_S2_DGRAD;
         if (d->upsample) { p.Dz /= 2; p.Dy /= 2; p.Dx /= 2; }
         slots = (size_t)p.nkb * 64;                         // 64 (class, entry) slots
-    } else if (bf16io && p.ks == 3 && p.stride == 1 && p.K <= 8 && p.O <= 32 && getenv("VDM4CDM_NO_KPACK") == nullptr) {
+    } else if (bf16io && p.ks == 3 && p.stride == 1 && p.K <= 8 && p.O <= 32 && kpack_enabled()) {
         p.layout = p.family = VDM_CONV_VARIANT_KPACK;      // tap-packed kernel, 4x8x16
         slots = 7;                                          // 7 groups of 4 taps
     } else if (p.stride == 2) {
-        p.tz = s2_tile_z(); p.ty = 4;
+        p.tz = 2; p.ty = 4;      // stride-2 conv: 2x4x16 output tile, a 5x9x33-voxel image (95 KB: one workgroup per CU)
     } else if (p.ks == 3) {      // (fp32 storage too since round 4: on the bf16 pipe it is no longer MFMA-bound, small grids need small tiles)
         small_grid_tile(p);
         if (bf16io && p.nc == 4) {
-            if (ksplit_tile(p)) p.family = VDM_CONV_VARIANT_KSPLIT;
+            if (uses_ksplit(p)) p.family = VDM_CONV_VARIANT_KSPLIT;
             else if (uses_split(p)) p.family = VDM_CONV_VARIANT_SPLIT;
         }
         if (bf16io && p.nc == 2 && p.tz == 4) {            // (NC = 4 needs > 128 registers per wave: its accumulators alone are 64)
             // rolling-z kernel: one K-block, large grid: persistent walk up z; VDM4CDM_ROLL=0 switches it off (A/B)
             static const bool roll_on = getenv("VDM4CDM_ROLL") ? atoi(getenv("VDM4CDM_ROLL")) != 0 : true;
-            // VDM4CDM_WG8: bit mask of the kernel classes that run eight-wave workgroups on the 4x8x16 tile - 1: plain, 2: folded GroupNorm backward
-            static const int wg8_mask = getenv("VDM4CDM_WG8") ? atoi(getenv("VDM4CDM_WG8")) : 0;
             p.roll = p.nkb == 1 && cdiv(p.Dz, 4) >= 4 && roll_on;
-            p.wg8 = p.roll ? 0 : (wg8_mask & 3);
         }
     }
     p.tiles = cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16) * (p.cls_kind == CLS_UP_FWD && p.family == VDM_CONV_VARIANT_CLASS ? 8 : 1);
@@ -1530,16 +1512,12 @@ static int env_int(const char* name, int dflt) { const char* e = getenv(name); r
 // persistent workgroups of a weight-gradient launch over all (cout, cin) block pairs (~2 per CU)
 static int wgrad_wgs() { static const int v = env_int("VDM4CDM_WGRAD_WGS", 512); return v > 0 ? v : 512; }
 // persistent workgroups of the thin-side kernel (4 waves each, one chunk per wave in flight ahead of the one it consumes)
-static int wgrad_thin_wgs() { static const int v = env_int("VDM4CDM_THIN_WGS", 512); return v > 0 ? v : 512; }
+constexpr int THIN_WORKGROUPS = 512;
 static bool wgrad_thin_enabled() { static const bool on = getenv("VDM4CDM_NO_THIN_WGRAD") == nullptr; return on; }
 // VDM4CDM_WGRAD_ROWS=0: the tap-split kernel also for the full bf16 3^3 stride-1 blocks
 static bool wgrad_rows_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROWS", 1) != 0; return on; }
 // VDM4CDM_WGRAD_ROLL=0: no rolling z window - the persistent workgroups of the rows kernel walk scattered tiles, not column segments
 static bool wgrad_roll_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROLL", 1) != 0; return on; }
-// stride 2: 1x4x16 output tiles (57-KB halo, two workgroups per CU; default since round 4: alone 0.100 -> 0.091 / 0.060 -> 0.048 / 0.038 ->
-// 0.034 ms at levels 0 / 1 / 2, step unchanged).  VDM4CDM_S2W_TZ=2: 2x4x16 tiles (95-KB halo, -17 % staged bytes, one workgroup per
-// CU - and none next to a main-stream kernel that holds 2 x 70 KB of the CU's LDS)
-static int wgrad_s2_tile_z() { static const int v = env_int("VDM4CDM_S2W_TZ", 1); return v == 1 ? 1 : 2; }
 // VDM4CDM_GROUPED_REDUCE: the grouped slab reduce also for few slabs (same result, other launch shape)
 static bool wgrad_grouped_only() { static const bool on = getenv("VDM4CDM_GROUPED_REDUCE") != nullptr; return on; }
 
@@ -1548,7 +1526,7 @@ static WgradPlan plan_wgrad_thin(int kernel, int n, int od, int oh, int ow, int 
     WgradPlan p{};
     p.kernel = kernel; p.ks = 3; p.stride = 1;
     long long want = ((long long)n * od * oh * cdiv(ow, 32) + 3) / 4;      // chunks of 32 x-consecutive voxels, one per wave
-    if (want > wgrad_thin_wgs()) want = wgrad_thin_wgs();
+    if (want > THIN_WORKGROUPS) want = THIN_WORKGROUPS;
     p.grid = p.P = (int)(want < 1 ? 1 : want);
     p.slab_bytes = (size_t)p.grid * cdense * THIN_COLS * sizeof(float);
     p.workspace_bytes = p.slab_bytes + (size_t)n * od * oh * ow * sizeof(uint32_t);
@@ -1575,7 +1553,8 @@ static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumul
     if (d->ksize == 1) {
         p.tz = 4; p.ty = 8; p.per_wg = 4; slots = 4;
     } else if (d->stride == 2) {
-        p.tz = wgrad_s2_tile_z(); p.ty = 4;
+        p.tz = 1; p.ty = 4;      // 1x4x16 output tiles (57-KB halo, two workgroups per CU; since round 4: alone 0.100 -> 0.091 /
+                                 // 0.060 -> 0.048 / 0.038 -> 0.034 ms at levels 0 / 1 / 2 against 2x4x16 tiles, step unchanged)
     } else if (d->upsample) {                    // 8 parity classes x 8 merged taps, everything on the coarse grid
         p.kernel = VDM_WGRAD_CLASS;              // (2x4x16 tiles with 1024 workgroups: same time)
         p.tz = 2; p.ty = 8;
@@ -1620,8 +1599,6 @@ int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s);
 int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s);
 int run_cls(const vdm_conv_desc* d, const Plan& p, const void* x, const void* w, const float* bias, const void* res, void* out,
             hipStream_t s, float* gn_partials = nullptr);
-// conv_wgrad.hip: fixed-order fold of the P per-workgroup slabs [P][27][32][32] (+ [P][32] bias partials) of conv_dgw.hip
-int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float* dbias, int P, int accumulate, hipStream_t s);
 // weight gradient by its plan.  w / a: operands, dims and channel counts; slabs, tile counts and P are the launcher's to fill from the plan
 int launch_wgrad_any(const WgradArgs& w, const WgradPlan& p, float* dw, float* dbias, int accumulate, size_t workspace_bytes, int dtype,
                      hipStream_t s);

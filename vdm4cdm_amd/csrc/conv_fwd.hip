@@ -12,15 +12,12 @@ namespace vdm {
 // GNB: the GroupNorm+SiLU backward reduction is folded into the epilogue (dgrad launches that feed a GroupNorm: conv_epilogue_gnb).
 // GNP: the conv input is silu(gn(x)) of the raw tensor x (inference): GroupNorm + SiLU are applied to the staged image in LDS
 // (gn_prologue_inplace) instead of by a pass of their own.
-// NW = 8 (large bf16 3x3x3 stride-1 grids): the SAME tile and LDS image shared by eight waves of NV = 4 rows - two workgroups per CU
-// are then four waves per SIMD (<= 128 registers each) instead of two: twice the waves to issue the staging DMA, to cover the
-// barrier-to-barrier phases of the co-resident workgroup and to drain the epilogue, at unchanged staged bytes per voxel.
-template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false, int NW = 4>
-__global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <= 2) ? 3 : 2)) conv_fwd_kernel(const ConvArgs a) {
+template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false>
+__global__ void __launch_bounds__(256, (TZ * TY <= 16 && NC <= 2) ? 3 : 2) conv_fwd_kernel(const ConvArgs a) {
     static_assert(!SPLIT || NC == 2, "half-chunk mode is the NC=2 kernel on NC=4 weights");
     static_assert(!(GNB && GNP), "the prologue belongs to forward convs, the folded backward to dgrad convs");
     constexpr int NCW = SPLIT ? 4 : NC;
-    using G = Geo<KS, STRIDE, TZ, TY, NW>;
+    using G = Geo<KS, STRIDE, TZ, TY>;
     constexpr int NV = G::NV, TAPS = G::TAPS;
     extern __shared__ __attribute__((aligned(16))) char lds[];
 
@@ -59,7 +56,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
     // the loads retire behind the first staging barrier instead of stalling the epilogue
     const int e_cout0 = SPLIT ? (chunk >> 1) * 64 + (chunk & 1) * 8 : chunk * NC * 16, e_qstride = SPLIT ? 16 : NC * 4;
     GnbRegs<T, NC, GNB ? NV : 1> gr;
-    constexpr bool GNB_PRE = GNB && NC <= 2 && NW == 4;      // (eight-wave workgroups: 128 registers per wave, the rolling window instead)
+    constexpr bool GNB_PRE = GNB && NC <= 2;
     float* gnb_tab = reinterpret_cast<float*>(lds + ((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES);      // (behind the GN scratch; read after the first barrier)
     if constexpr (GNB && VDM_GNB_TABLE) gnb_consts_table(gnb_tab, a, n, e_cout0, tid);
     if constexpr (GNB_PRE) gnb_issue<T, G, NC, NV, VDM_GNB_TABLE != 0>(gr, a, n, oz0, oy0, ox0, wave, lane, e_cout0, e_qstride);
@@ -69,7 +66,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
     for (int kb = 0; kb < a.nkb; ++kb) {
         if (kb) __syncthreads();
         if constexpr (GNP)      // (the in-place GroupNorm prologue re-walks the chunks a wave staged: the chunk walk)
-            stage_halo_dma_chunks<T, G, UPS, NW>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
+            stage_halo_dma_chunks<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
         else
             stage_halo_dma<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane);
         if (kb == 0) VDM_STAMP(6);
@@ -77,7 +74,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
         float* gn_tab = reinterpret_cast<float*>(lds + IMG_ + GN_SCRATCH_BYTES);
         if constexpr (GNP) {
             if (kb == 0) {                                  // (behind the first DMA issue: the table is built while the halo is in flight)
-                gn_prologue_table(gn_tab, a, n, tid, 64 * NW);
+                gn_prologue_table(gn_tab, a, n, tid, 64 * G::NW);
                 __syncthreads();
             }
         }
@@ -89,7 +86,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
             if constexpr (RR) rr_prefetch_weights<NC, WPD, NCW>(wf, wk);
             else taps_prefetch_weights<TAPS, NC, WPD, NCW>(wf, wk);
             if (kb == 0) VDM_STAMP(1);
-            if constexpr (GNP) gn_prologue_inplace<T, G, NW>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
+            if constexpr (GNP) gn_prologue_inplace<T, G>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
             __syncthreads();
             if (kb == 0) VDM_STAMP(2);
 #ifdef VDM_TAP_PRIO
@@ -101,7 +98,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
             __builtin_amdgcn_s_setprio(0);
 #endif
         } else {
-            if constexpr (GNP) gn_prologue_inplace<T, G, NW>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
+            if constexpr (GNP) gn_prologue_inplace<T, G>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
             __syncthreads();
             taps_rolled<T, G, NC, NV>(acc, lds, wk, lanex);
         }
@@ -119,7 +116,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((TZ * TY <= 16 && NC <
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the stores of the epilogue have left the wave's queue)
     VDM_STAMP(4);
     if (a.stamps && lane == 0) {
-        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * NW + wave) * 8;
+        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * G::NW + wave) * 8;
         for (int k = 0; k < 7; ++k) o[k] = tl_t[k];
         o[7] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
     }
@@ -407,16 +404,15 @@ __global__ void __launch_bounds__(256, GNB ? 2 : 4) conv_kpack_kernel(const Conv
                                         (tz * a.nty + ty) * a.ntx + tx, chunk * NC * 16, NC * 4);
 }
 
-template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false, int NW = 4>
+template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false>
 static int launch_fwd_cfg(const ConvArgs& a0, hipStream_t s) {
-    using G = Geo<KS, STRIDE, TZ, TY, NW>;
+    using G = Geo<KS, STRIDE, TZ, TY>;
     ConvArgs a = a0;
     if (SPLIT) a.nchunks *= 2;
     a.ntz = cdiv(a.Dz, TZ); a.nty = cdiv(a.Dy, TY); a.ntx = cdiv(a.Dx, 16);
     set_tile_divs(a);
-    static const int lds_pad = getenv("VDM4CDM_LDS_PAD") ? atoi(getenv("VDM4CDM_LDS_PAD")) : 0;      // experiments: fewer workgroups per CU
-    const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES + (GNP ? GNP_TABLE_BYTES : 0) + (GNB ? GNB_TABLE_BYTES : 0) + (size_t)(lds_pad > 0 ? lds_pad : 0);
-    auto kern = conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB, GNP, NW>;
+    const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES + (GNP ? GNP_TABLE_BYTES : 0) + (GNB ? GNB_TABLE_BYTES : 0);
+    auto kern = conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB, GNP>;
     static unsigned long long lds_done = 0;
     {
         int e = set_lds(kern, lds, lds_done);
@@ -427,7 +423,7 @@ static int launch_fwd_cfg(const ConvArgs& a0, hipStream_t s) {
 #ifdef VDM_TIMELINE
     a.stamps = g_timeline_stamps;
 #endif
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * NW), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(64 * G::NW), lds, s, a);
     VDM_LAUNCH_CHECK("conv_fwd_kernel");
     return VDM_OK;
 }
@@ -485,7 +481,7 @@ template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, bool GNB
 static int launch_fwd_geo(const ConvArgs& a, const Plan& p, hipStream_t s) {
     const int tz = p.tz, ty = p.ty;
     if constexpr (STRIDE == 2)
-        return tz == 1 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 4>(a, s);
+        return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 4>(a, s);
     else if constexpr (KS == 3) {
         if constexpr (NC == 4 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2) {
             if (p.family == VDM_CONV_VARIANT_KSPLIT) {
@@ -501,7 +497,6 @@ static int launch_fwd_geo(const ConvArgs& a, const Plan& p, hipStream_t s) {
         if (tz == 2) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 8, false, GNB, GNP>(a, s);
         if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2 && !GNP) {      // (the prologue runs on the plain 4x8x16 kernel)
             if (p.roll) return launch_roll<T, NC, GNB>(a, s);
-            if ((p.wg8 >> (GNB ? 1 : 0)) & 1) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP, 8>(a, s);
         }
         return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP>(a, s);
     } else

@@ -599,27 +599,12 @@ template <typename T>
 static int launch_wgrad(const WgradArgs& w, const WgradPlan& p, float* dw, float* db, int acc, hipStream_t s) {
     if (p.kernel == VDM_WGRAD_CLASS) return launch_wgrad_cfg<T, 3, 1, 2, 2, 8>(w, p, dw, db, acc, s);
     if (p.ks == 1) return launch_wgrad_cfg<T, 1, 1, 0, 4, 8>(w, p, dw, db, acc, s);
-    if (p.stride == 2) return p.tz == 1 ? launch_wgrad_cfg<T, 3, 2, 0, 1, 4>(w, p, dw, db, acc, s) : launch_wgrad_cfg<T, 3, 2, 0, 2, 4>(w, p, dw, db, acc, s);
+    if (p.stride == 2) return launch_wgrad_cfg<T, 3, 2, 0, 1, 4>(w, p, dw, db, acc, s);
     if constexpr (sizeof(T) == 2) {
         if (p.ntb == 1) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 2, 1>(w, p, dw, db, acc, s);
         if (p.nta == 1) return launch_wgrad_cfg<T, 3, 1, 0, 2, 8, 1, 2>(w, p, dw, db, acc, s);
     }
     return launch_wgrad_cfg<T, 3, 1, 0, 2, 8>(w, p, dw, db, acc, s);
-}
-
-int launch_dgw_reduce(const float* slabs, const float* bslabs, float* dw, float* dbias, int P, int accumulate, hipStream_t s) {
-    const int total = 27 * 32 * 32;
-    if (ablate_reduce()) return VDM_OK;
-    if (P <= 32)
-        hipLaunchKernelGGL(wgrad_reduce_direct_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, slabs, dw, 27, 32, 32, 1, 1, 32, P, accumulate);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, WRED_OUT)), dim3(256), 0, s, slabs, dw, 27, 32, 32, 1, 1, 32, P, accumulate);
-    VDM_LAUNCH_CHECK("wgrad_reduce_kernel(dgw)");
-    if (dbias) {
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3(2), dim3(256), 0, s, bslabs, dbias, 32, 32, P, accumulate);
-        VDM_LAUNCH_CHECK("wgrad_bias_reduce_kernel(dgw)");
-    }
-    return VDM_OK;
 }
 
 int launch_wgrad_any(const WgradArgs& w, const WgradPlan& p, float* dw, float* dbias, int accumulate, size_t workspace_bytes, int dtype,

@@ -20,14 +20,8 @@ FUSED_GN = os.environ.get("VDM4CDM_FUSED_GN", "1") != "0"
 # GroupNorm backward reduction folded into the producing dgrad conv's epilogue (VDM4CDM_FUSED_GNB=0: separate reduce pass with
 # float atomics, for A/B timing).  Needs the forward partials (FUSED_GN) for the analytic conditioning-table gradient.
 FUSED_GNB = FUSED_GN and os.environ.get("VDM4CDM_FUSED_GNB", "1") != "0"
-GNB_MIN_K = int(os.environ.get("VDM4CDM_GNB_MIN_K", "0"))      # fold only into dgrad convs with at least this many reduction channels
 # the 1x1x1 skip conv of a ResNetBlock rides along with norm1's GroupNorm passes where csrc/gn_skip.hip has a kernel (bf16, narrow layers)
 FUSED_SKIP = os.environ.get("VDM4CDM_FUSED_SKIP", "1") != "0"
-# input gradient (+ folded GroupNorm backward) and weight gradient of a 32 -> 32 conv as ONE launch that stages the gradient once
-# (csrc/conv_dgw.hip; the level-0 convs of the 128^3 network).  Opt-in (VDM4CDM_FUSED_DGW=1) since the stand-alone weight-gradient kernel
-# got its rolling z window and copy-free operand tuples: alone 0.55 ms fused against 0.345 + 0.213 ms separately, training step 12.23 fused
-# against 12.02 ms separate (same box, alternating)
-FUSED_DGW = os.environ.get("VDM4CDM_FUSED_DGW", "0") == "1"
 # inference: norm2's GroupNorm + SiLU applied inside conv2 (to the staged halo image) instead of by a pass of its own.  Measured: the
 # VALU work on the 2.1x halo costs the conv what the 5 TB/s pass cost - off by default
 # "0" (default): nowhere; "deep": only at the levels of <= 32^3 voxels; "1": everywhere.  Round 4, same box, 300 sampling steps at 128^3:
@@ -180,7 +174,7 @@ class _Res:
         i, G, n = self.i, self.net.norm_groups, self.i.name
         x1, x2, st1, a1, h, st2, a2, p, seed, mask2 = self.saved
         self.saved = None
-        fused = (FUSED_GNB and getattr(st2, "chsum", None) is not None and (p == 0.0 or mask2 is not None) and i.cout >= GNB_MIN_K
+        fused = (FUSED_GNB and getattr(st2, "chsum", None) is not None and (p == 0.0 or mask2 is not None)
                  and self.conv2.gn_fold_ok(i.cout, 0, h.dtype) and self.conv1.gn_fold_ok(i.c1, i.c2, h.dtype))
 
         skip_grads = []
@@ -191,27 +185,18 @@ class _Res:
                 skip_grads.append(self.skip2.dgrad(dout) if self.skip2 is not None else None)
             ss.second.run(side_skip_dgrad, dout)
 
-        dgw2 = fused and FUSED_DGW and self.conv2.dgw_ok(dout, i.cout, 0)      # conv2: both gradients from one staging of dout
         tcols = dtable[:, i.table_off:i.table_off + i.cout]
-        if dgw2:
-            dyh2 = self.conv2.dgrad_gn_wgrad(dout, a2, h, None, G, st2, P(n + ".norm2.weight"), P(n + ".norm2.bias"), GP(n + ".conv2.weight"),
-                                             GP(n + ".conv2.bias"), keep_mask=mask2, dropout_p=p)
 
         def side_conv2(a2=a2, dout=dout, x1=x1, x2=x2):      # conv2 (+ the 1x1 skip convs share dout); tensors bound now: may run deferred
-            if not dgw2:
-                self.conv2.wgrad(a2, dout, GP(n + ".conv2.weight"), GP(n + ".conv2.bias"))      # bias grad fused (column sums of dout)
+            self.conv2.wgrad(a2, dout, GP(n + ".conv2.weight"), GP(n + ".conv2.bias"))      # bias grad fused (column sums of dout)
             if self.skip1 is not None:
                 GP(n + ".skip.bias").copy_(GP(n + ".conv2.bias"))          # same column sums of dout
                 if not ride:
                     self.skip1.wgrad(x1, dout, GP(n + ".skip.weight"))
                     if self.skip2 is not None:
                         self.skip2.wgrad(x2, dout, GP(n + ".skip2.weight"))
-        if not dgw2 or self.skip1 is not None:
-            ss.run(side_conv2, a2, dout, x1, x2)
-        if dgw2:
-            dh, _ = ops.gn_bwd_fused(h, None, G, st2, P(n + ".norm2.weight"), dyh2, GP(n + ".norm2.weight"), GP(n + ".norm2.bias"),
-                                     colsum=tcols)
-        elif fused:      # dgrad epilogue: dyh = da2 * keep * silu'(.) + per-tile sums; then one finalize + one apply pass (no atomics)
+        ss.run(side_conv2, a2, dout, x1, x2)
+        if fused:      # dgrad epilogue: dyh = da2 * keep * silu'(.) + per-tile sums; then one finalize + one apply pass (no atomics)
             dyh2 = self.conv2.dgrad_gn(dout, h, None, G, st2, P(n + ".norm2.weight"), P(n + ".norm2.bias"), keep_mask=mask2, dropout_p=p)
             dh, _ = ops.gn_bwd_fused(h, None, G, st2, P(n + ".norm2.weight"), dyh2, GP(n + ".norm2.weight"), GP(n + ".norm2.bias"),
                                      colsum=tcols)
@@ -221,14 +206,11 @@ class _Res:
                                     GP(n + ".norm2.weight"), GP(n + ".norm2.bias"), colsum=tcols, dropout_p=p, seed=seed, dx1=da2)
         del a2
         # conv1
-        if fused and FUSED_DGW and self.conv1.dgw_ok(dh, i.c1, i.c2):
-            dyh1 = self.conv1.dgrad_gn_wgrad(dh, a1, x1, x2, G, st1, P(n + ".norm1.weight"), P(n + ".norm1.bias"), GP(n + ".conv1.weight"))
+        ss.run(lambda a1=a1, dh=dh: self.conv1.wgrad(a1, dh, GP(n + ".conv1.weight")), a1, dh)
+        if fused:
+            dyh1 = self.conv1.dgrad_gn(dh, x1, x2, G, st1, P(n + ".norm1.weight"), P(n + ".norm1.bias"))
         else:
-            ss.run(lambda a1=a1, dh=dh: self.conv1.wgrad(a1, dh, GP(n + ".conv1.weight")), a1, dh)
-            if fused:
-                dyh1 = self.conv1.dgrad_gn(dh, x1, x2, G, st1, P(n + ".norm1.weight"), P(n + ".norm1.bias"))
-            else:
-                da1 = self.conv1.dgrad(dh)
+            da1 = self.conv1.dgrad(dh)
         del a1, dh
         # skip path
         add1 = add2 = None
