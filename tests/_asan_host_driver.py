@@ -51,14 +51,12 @@ def plan_everything(d):
     t1, t2 = L.vdm_conv_gn_tiles(d), L.vdm_conv_dgrad_gn_tiles(d)
     ws = L.vdm_conv_wgrad_workspace_bytes(d)
     assert t1 >= 0 and t2 >= 0 and ws >= 0
-    gn_ok = L.vdm_conv_fwd_gn_supported(d)
     if L.vdm_conv_packed_bytes(d, 0):          # accepted descriptor
         assert t1 > 0 and ws > 0, (t1, ws)
         assert (t2 > 0) == (d.ksize == 3 and d.stride == 1 and not d.upsample), t2          # only those convs feed a GroupNorm backward
-        assert not gn_ok or variant[0] in (0, 3), variant          # GroupNorm prologue: generic kernel or its half-chunk form only
     else:
-        assert t1 == 0 and t2 == 0 and not gn_ok
-    calls += 5
+        assert t1 == 0 and t2 == 0
+    calls += 4
 
 
 # 1. the shapes of the network family, every (ksize, stride, upsample, dtype, pad) the product uses

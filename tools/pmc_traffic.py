@@ -23,7 +23,7 @@ def simplify(name):
     m = re.search(r"conv_roll_kernel<vdm::(\w+), (\d), (true|false)>", name)
     if m:
         return f"conv_fwd_kernel<{m.group(1)},k3,s1,NC{m.group(2)}>" + ("+gnb" if m.group(3) == "true" else "")
-    # conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB, GNP, NW>
+    # conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB> (the optional tail also matches the longer lists of older profiles)
     m = re.search(r"conv_fwd_kernel<vdm::(\w+), (?:vdm::)?(\w+), (\d), (\d), (\d), (\d), \d+, \d+(?:, (true|false))?(?:, (true|false))?(?:, (?:true|false))?(?:, \d+)?>", name)
     if m:
         return (f"conv_fwd_kernel<{m.group(1)},k{m.group(3)},s{m.group(4)},NC{m.group(6)}{',split' if m.group(7) == 'true' else ''}>"

@@ -79,7 +79,7 @@ PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _T = C.POINTER(DdnmTables)
-ABI_VERSION = 19                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 20                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -92,8 +92,6 @@ SIGNATURES = {
     "vdm_conv_pack_many": (_i, [_p, _p, _i, _i, _p]),
     "vdm_conv_gn_tiles": (_i, [_D]),
     "vdm_conv_fwd": (_i, [_D, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
-    "vdm_conv_fwd_gn_supported": (_i, [_D]),
-    "vdm_conv_fwd_gn": (_i, [_D, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _i, _f, _p]),
     "vdm_conv_dgrad": (_i, [_D, _p, _p, _p, _p, _p]),
     "vdm_conv_dgrad_gn_tiles": (_i, [_D]),
     "vdm_conv_dgrad_gn": (_i, [_D, _p, _p, _p, C.POINTER(GnFold), _p]),

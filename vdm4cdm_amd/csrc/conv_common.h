@@ -26,7 +26,6 @@
 namespace vdm {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-static constexpr int GNP_TABLE_BYTES = 512 * 2 * 4;          // GroupNorm prologue: (A, B) of up to 512 input channels
 static constexpr int GN_SCRATCH_BYTES = 8 * 64 * 2 * 4;      // <= 8 waves x (NC <= 4) * 16 channels x (sum, sumsq) floats
 
 // ---------------------------------------------------------------------------------------------
@@ -124,81 +123,21 @@ static __device__ uint4 g_zero_page[16];
 // (dz, dy, row) shifts stay compile-time ds_read offsets.
 // Filled by LDS-DMA (global_load_lds_dwordx4): one wave-instruction = 16 voxels x 64 B = 1 KiB of LDS written
 // linearly; the four lanes of a voxel fetch its (permuted) pieces, i.e. whole 64-B segments of the NDHWC row.
-//
-// The address arithmetic of the ~17 chunks a wave stages is on the critical path of every tile (tools/conv_timeline.py: a
-// workgroup used to spend 5 of its 17 us between kernel entry and the last DMA issue): the halo coordinate (hz, hy, hx) of a
-// lane advances by a CONSTANT from chunk to chunk (64 halo voxels), so it is carried incrementally (adds + two conditional
-// carries, no division), and the voxel offset inside the sample is 32-bit with 24-bit multiplies (full-rate v_mul_u32_u24;
-// 32-bit integer multiplies are quarter rate).  The host checks that a sample's elements fit 32 bits.
-// ss / so*: logical voxel i maps to source voxel ss * i + so (class sub-grid of the per-parity-class kernels when ss == 2);
-// sD*: source tensor dims.
-// NWAVES: waves that share the chunks (4: all waves of a workgroup; 1: a wave stages a private image - conv_ksplit_kernel).
-template <typename T, typename G, int UPS, int NWAVES = 4>
-__device__ __forceinline__ void stage_halo_dma_chunks(char* lds, const T* __restrict__ x, const ConvArgs& a, int n, int oz0, int oy0,
-                                                      int ox0, int kb, int wave, int lane, int ss, int soz, int soy, int sox, int sDz,
-                                                      int sDy, int sDx) {
-    constexpr int EPL = DT<T>::EPL, KB = DT<T>::KB;
-    constexpr int NCHUNK = (G::HVOX + 15) / 16;
-    constexpr int STEP = 16 * NWAVES;                       // halo voxels between two chunks of one wave
-    constexpr int DX = STEP % G::HX, DY = (STEP / G::HX) % G::HY, DZ = STEP / (G::HX * G::HY);
-    const int iz0 = oz0 * G::STRIDE - G::PAD, iy0 = oy0 * G::STRIDE - G::PAD, ix0 = ox0 * G::STRIDE - G::PAD;
-    const int k = lane >> 2, j = lane & 3;
-    const int hv0 = wave * 16 + k;                          // first chunk of this wave (constant divisors: once per call)
-    int hx = hv0 % G::HX, hy = (hv0 / G::HX) % G::HY, hz = hv0 / (G::HX * G::HY);
-    const T* xn = x + (size_t)n * ((size_t)sDz * sDy * sDx * a.CinStride);
-    const bool fastwrap = a.Iz >= G::HZ && a.Iy >= G::HY && a.Ix >= G::HX;      // one conditional add / subtract wraps
-    for (int c = wave; c < NCHUNK; c += NWAVES) {
-        const int pc = j ^ ((hx >> 1) & 3);
-        const int ci = kb * KB + pc * EPL;
-        int iz = iz0 + hz, iy = iy0 + hy, ix = ix0 + hx;
-        bool ok = ci < a.Cin && hz < G::HZ;                 // (hz < HZ <=> the chunk's tail is inside the halo)
-        if (a.circular) {
-            if (fastwrap) {
-                iz += iz < 0 ? a.Iz : 0; iz -= iz >= a.Iz ? a.Iz : 0;
-                iy += iy < 0 ? a.Iy : 0; iy -= iy >= a.Iy ? a.Iy : 0;
-                ix += ix < 0 ? a.Ix : 0; ix -= ix >= a.Ix ? a.Ix : 0;
-            } else {
-                iz = wrap(iz, a.Iz); iy = wrap(iy, a.Iy); ix = wrap(ix, a.Ix);
-            }
-        } else {
-            ok = ok && (unsigned)iz < (unsigned)a.Iz && (unsigned)iy < (unsigned)a.Iy && (unsigned)ix < (unsigned)a.Ix;
-        }
-        if (UPS) { iz >>= 1; iy >>= 1; ix >>= 1; }
-        const unsigned sz = (unsigned)(ss * iz + soz) & 0xffffffu, sy = (unsigned)(ss * iy + soy) & 0xffffffu,
-                       sx = (unsigned)(ss * ix + sox) & 0xffffffu;      // (masked: garbage of !ok lanes stays a legal u24 operand)
-        const unsigned row = __umul24(sz, (unsigned)sDy) + sy;
-        const unsigned vox = __umul24(row, (unsigned)sDx) + sx;
-        const unsigned eoff = vox * (unsigned)a.CinStride + (unsigned)ci;
-        const void* src = ok ? static_cast<const void*>(xn + eoff) : static_cast<const void*>(g_zero_page);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(lds + c * 1024), 16, 0, 0);
-        hx += DX; hy += DY; hz += DZ;
-        if (hx >= G::HX) { hx -= G::HX; hy += 1; }
-        if (hy >= G::HY) { hy -= G::HY; hz += 1; }
-    }
-}
-
-
+// The voxel offset inside a sample is 32-bit with 24-bit multiplies (full-rate v_mul_u32_u24; 32-bit integer multiplies are quarter
+// rate).  The host checks that a sample's elements fit 32 bits.
 // ---------------------------------------------------------------------------------------------
 // Row-wise staging (round 4).  Counters (profiles/r04_pmc_mfma_util.json): the level-0 conv issued 2 070 vector instructions per wave
-// and tile next to its 432 MFMAs, and about half of them were the address arithmetic of the chunk walk above - it re-derives
-// (hz, hy, hx), the wrap / bounds tests, two 24-bit multiplies and a 64-bit pointer select per lane for every one of a wave's 17
-// chunks, because a 16-voxel chunk of the linear halo image straddles two halo rows.  A SIMD issues one vector instruction per 4
-// cycles from a wave and an MFMA holds the issue port for 8 of its 16: the staging arithmetic of one workgroup costs the co-resident
+// and tile next to its 432 MFMAs, and about half of them were the address arithmetic of the earlier walk over 16-voxel chunks of the
+// linear image - it re-derived (hz, hy, hx), the wrap / bounds tests, two 24-bit multiplies and a 64-bit pointer select per lane for
+// every one of a wave's 17 chunks, because such a chunk straddles two halo rows.  A SIMD issues one vector instruction per 4
+// cycles from a wave and an MFMA holds the issue port for 8 of its 16: the staging arithmetic of one workgroup cost the co-resident
 // workgroup's tap loop about as many issue slots as the taps themselves (why "fewer staged chunks" bought 8-11 % and more waves nothing).
-// Same LDS image, another walk: a halo ROW (hz, hy) is wave-uniform, so its validity, its wrap and its source address are SCALAR
+// Same LDS image, walked by rows: a halo ROW (hz, hy) is wave-uniform, so its validity, its wrap and its source address are SCALAR
 // arithmetic (the scalar unit is otherwise idle); per lane only the x offset of its voxel / piece remains, and that is the same for
 // every row - computed once per tile.  Per row: NSEG LDS-DMAs of 16 voxels (16 B per lane, hx = 16 s ... 16 s + 15) and, for the
 // HX - 16 NSEG leftover voxels at the end of the row (hx = 16, 17 of an 18-voxel row), ONE 4-byte-per-lane LDS-DMA with 16 lanes per
 // voxel active (the leftover voxels of a row are contiguous in the image; masked lanes write nothing).
 // ---------------------------------------------------------------------------------------------
-#ifndef VDM_ROWSTAGE
-#define VDM_ROWSTAGE 1
-#endif
-// leftover voxels of a row: 0 = one 4-byte-per-lane LDS-DMA (16 lanes per voxel), 1 = one 16-byte-per-lane LDS-DMA (4 lanes per voxel)
-#ifndef VDM_TAIL16
-#define VDM_TAIL16 0
-#endif
 // per-lane x part (once per tile / per persistent workgroup) + one halo row per call
 template <typename T, typename G, int UPS>
 struct RowStager {
@@ -234,13 +173,9 @@ struct RowStager {
 #pragma unroll
         for (int sgm = 0; sgm < NSEG; ++sgm) okx[sgm] = xpart(16 * sgm + (lane >> 2), lane & 3, xoff[sgm]);
         if constexpr (NTAIL > 0) {
-#if VDM_TAIL16
-            tok = xpart(16 * NSEG + ((lane >> 2) & 3), lane & 3, toff) && lane < 4 * NTAIL;      // 16 B per lane, 4 lanes per leftover voxel
-#else
             const int d = lane & 15;                                          // dword of the tail voxel lane >> 4
             tok = xpart(16 * NSEG + (lane >> 4), d >> 2, toff) && lane < 16 * NTAIL;
             toff += (unsigned)(d & 3) * 4u;
-#endif
         }
     }
     // halo row (hz, hy) of the tile (wave-uniform) -> LDS row `lrow` (HX * 64 bytes): NSEG (+1) LDS-DMAs, scalar address arithmetic
@@ -263,23 +198,13 @@ struct RowStager {
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(lrow + sgm * 1024), 16, 0, 0);
         }
-#ifndef VDM_EXP_NOTAIL                                                        // (timing experiment: rows without their leftover voxels)
         if constexpr (NTAIL > 0) {
-#if VDM_TAIL16
-            if (lane < 4 * NTAIL) {
-                const char* src = (okrow && tok) ? rowp + toff : zp;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(lrow + NSEG * 1024), 16, 0, 0);
-            }
-#else
             if (lane < 16 * NTAIL) {
                 const char* src = (okrow && tok) ? rowp + toff : zp;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(lrow + NSEG * 1024), 4, 0, 0);
             }
-#endif
         }
-#endif
     }
 };
 
@@ -292,67 +217,14 @@ __device__ __forceinline__ void stage_halo_dma_rows(char* lds, const T* __restri
     for (int r = wave; r < NROW; r += NWAVES) st.row(lds + r * (G::HX * 64), a, r / HY, r % HY);
 }
 
+// ss / so*: logical voxel i maps to source voxel ss * i + so (class sub-grid of the per-parity-class kernels when ss == 2);
+// sD*: source tensor dims.
+// NWAVES: waves that share the rows (4: all waves of a workgroup; 1: a wave stages a private image - conv_ksplit_kernel).
 template <typename T, typename G, int UPS, int NWAVES = 4>
 __device__ __forceinline__ void stage_halo_dma_gen(char* lds, const T* __restrict__ x, const ConvArgs& a, int n, int oz0, int oy0,
                                                    int ox0, int kb, int wave, int lane, int ss, int soz, int soy, int sox, int sDz,
                                                    int sDy, int sDx) {
-#if VDM_ROWSTAGE
     stage_halo_dma_rows<T, G, UPS, NWAVES>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, ss, soz, soy, sox, sDz, sDy, sDx);
-#else
-    stage_halo_dma_chunks<T, G, UPS, NWAVES>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, ss, soz, soy, sox, sDz, sDy, sDx);
-#endif
-}
-
-// GroupNorm + SiLU applied to the staged halo image in place (inference: the conv input is silu(gn(x)) of a tensor nobody else
-// needs activated - the separate gn_silu_fwd pass, one read + one write of the tensor, disappears).  Every wave transforms exactly
-// the chunks it staged itself (same chunk / lane walk as stage_halo_dma_gen), so its own `s_waitcnt vmcnt(0)` is all the
-// synchronisation needed before the workgroup barrier in front of the taps.  Voxels outside the volume came from the zero page and
-// stay zero (the conv pads the ACTIVATED tensor).  tab: LDS, [0, Cin) = A = rstd * gamma, [Cin, 2 Cin) = B = beta - mean * A of
-// this sample.  The arithmetic is gn_silu_fwd's: the conv sees bit-identical operands.
-template <typename T, typename G, int NWAVES = 4>
-__device__ __forceinline__ void gn_prologue_inplace(char* lds, const float* tab, const ConvArgs& a, int oz0, int oy0, int ox0, int kb,
-                                                    int wave, int lane) {
-    static_assert(G::STRIDE == 1, "prologue: stride-1 convs only");
-    constexpr int EPL = DT<T>::EPL, KB = DT<T>::KB;
-    constexpr int NCHUNK = (G::HVOX + 15) / 16;
-    constexpr int STEP = 16 * NWAVES;
-    constexpr int DX = STEP % G::HX, DY = (STEP / G::HX) % G::HY, DZ = STEP / (G::HX * G::HY);
-    const int iz0 = oz0 - G::PAD, iy0 = oy0 - G::PAD, ix0 = ox0 - G::PAD;
-    const int k = lane >> 2, j = lane & 3;
-    const int hv0 = wave * 16 + k;
-    int hx = hv0 % G::HX, hy = (hv0 / G::HX) % G::HY, hz = hv0 / (G::HX * G::HY);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's LDS-DMA chunks have landed
-    for (int c = wave; c < NCHUNK; c += NWAVES) {
-        const int pc = j ^ ((hx >> 1) & 3);
-        const int ci = kb * KB + pc * EPL;
-        const int iz = iz0 + hz, iy = iy0 + hy, ix = ix0 + hx;
-        bool ok = ci < a.Cin && hz < G::HZ;
-        if (!a.circular) ok = ok && (unsigned)iz < (unsigned)a.Iz && (unsigned)iy < (unsigned)a.Iy && (unsigned)ix < (unsigned)a.Ix;
-        if (ok) {
-            uint4* q = reinterpret_cast<uint4*>(lds + c * 1024 + lane * 16);
-            Piece<T> px;
-            px.load(*q);
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) px.f[e] = silu_f(px.f[e] * tab[ci + e] + tab[a.Cin + ci + e]);
-            *q = px.store();
-        }
-        hx += DX; hy += DY; hz += DZ;
-        if (hx >= G::HX) { hx -= G::HX; hy += 1; }
-        if (hy >= G::HY) { hy -= G::HY; hz += 1; }
-    }
-}
-
-// the per-channel affines of sample n for gn_prologue_inplace (all threads of the workgroup; a barrier must follow)
-__device__ __forceinline__ void gn_prologue_table(float* tab, const ConvArgs& a, int n, int tid, int nthreads) {
-    const int gs = a.Cin / a.gG;
-    for (int c = tid; c < a.Cin; c += nthreads) {
-        const float sum = a.gstats[((size_t)n * a.gG + c / gs) * 2], sq = a.gstats[((size_t)n * a.gG + c / gs) * 2 + 1];
-        const float mean = sum / a.gcnt;
-        const float rstd = rsqrtf(fmaxf(sq / a.gcnt - mean * mean, 0.f) + a.geps);
-        const float A = rstd * a.ggamma[c];
-        tab[c] = A;
-        tab[a.Cin + c] = a.gbeta[c] - mean * A;
-    }
 }
 
 template <typename T, typename G, int UPS>
@@ -421,14 +293,8 @@ __device__ __forceinline__ void operand_lane_offsets(int (&lanex)[G::KS], int cw
 // Weight prefetch depth (taps ahead; ring of WPD + 1 register sets).  The packed weights are L1/L2 hits, but a CU's vector L1
 // returns hits IN ORDER behind the HBM misses of every other wave of the CU (tools/tcp_order_probe.hip: a hit takes 156 cycles
 // on an idle CU and ~1000-1300 while another wave keeps 16 LDS-DMA pieces in flight - which is what the co-resident workgroup
-// does while it stages its halo).  -DVDM_WPD_NC2 / -DVDM_WPD_NC4 override for experiments (make variant).
-#ifndef VDM_WPD_NC2
-#define VDM_WPD_NC2 2
-#endif
-#ifndef VDM_WPD_NC4
-#define VDM_WPD_NC4 1
-#endif
-template <int NC> struct WPipe { static constexpr int WPD = (NC <= 2) ? VDM_WPD_NC2 : VDM_WPD_NC4; };
+// does while it stages its halo).
+template <int NC> struct WPipe { static constexpr int WPD = (NC <= 2) ? 2 : 1; };
 
 // bf16: first WPD taps' weights (issued before the staging barrier so their latency overlaps it)
 template <int TAPS, int NC, int WPD, int NCW = NC>
@@ -487,9 +353,6 @@ __device__ __forceinline__ void taps_pipelined(f32x4 (&acc)[NV][NC], const char*
 // 4 waves x 8) as MFMA clocks (16 MFMAs x 16) per tap - before the LDS-DMA writes of the co-resident workgroup; this order cuts
 // the operand reads 2.4x.  Execution order: group g = (dz, dx), then dy; a row register dies after its dy = 2 use, and the same
 // row of the NEXT group is loaded right there (ring of NV + 2 fragments: 40 VGPRs instead of the 64 of two full sets).
-#ifndef VDM_ROWREUSE
-#define VDM_ROWREUSE 1
-#endif
 __host__ __device__ constexpr int rr_tap(int e) { return ((e / 3) / 3) * 9 + (e % 3) * 3 + ((e / 3) % 3); }     // execution slot -> tap (dz, dy, dx)
 
 template <int NC, int WPD, int NCW = NC>
@@ -873,12 +736,6 @@ __device__ __forceinline__ void st_sub(T* p, const float (&f)[SUB]) {
 // after it (NC = 4: the operand registers of the tap loop are free by then).
 // The second sum is taken against the RAW x (S2raw = sum dyh * x); vdm_gn_bwd_finalize converts the tile totals,
 // sum dyh * xhat = rstd * (S2raw - mean * S1), so the inner loop needs neither xhat nor the per-group constants.
-#ifndef VDM_GNB_PACKED
-#define VDM_GNB_PACKED 1
-#endif
-#ifndef VDM_GNB_TABLE
-#define VDM_GNB_TABLE 1
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <typename T, int NC, int NV>
 struct GnbRegs {
@@ -987,7 +844,8 @@ __device__ __forceinline__ void gnb_consts_read(GnbRegs<T, NC, NV>& r, const flo
     }
 }
 
-// everything up front (NC <= 2, before the tap loop); ctab != nullptr: the constants come from the workgroup's table (gnb_consts_read, later)
+// everything up front (NC <= 2, before the tap loop).  TABLED (conv_fwd_kernel, conv_roll_kernel): the constants come from the workgroup's
+// table (gnb_consts_read, later); the K-split and tap-packed kernels have no table in their LDS layout and evaluate them per lane
 template <typename T, typename G, int NC, int NV, bool TABLED = false>
 __device__ __forceinline__ void gnb_issue(GnbRegs<T, NC, NV>& r, const ConvArgs& a, int n, int oz0, int oy0, int ox0, int cwave, int lane,
                                           int cout0, int qstride) {
@@ -1052,7 +910,7 @@ __device__ __forceinline__ void conv_epilogue_gnb(const f32x4 (&acc)[NV][NC], co
         if (!rm.ok(a, v) || !lane_ok) continue;
         const unsigned vox = rm.vox(a, v);
         const uint32_t mb = r.mb[v];
-        if constexpr (sizeof(T) == 2 && VDM_GNB_PACKED) {
+        if constexpr (sizeof(T) == 2) {
             // bf16 storage: explicit channel PAIRS (2i, 2i + 1) - one dword of x, two adjacent accumulator registers, one dword of dyh - so that
             // every arithmetic step is one packed instruction on registers that are already adjacent (the auto-vectorised scalar form paired
             // channels (0, 2), (1, 3) of the unpacked words and re-paired them with ~6 v_mov per pair: 5.2 k instructions per tile at NC = 4,
@@ -1107,7 +965,7 @@ __device__ __forceinline__ void conv_epilogue_gnb(const f32x4 (&acc)[NV][NC], co
             st_sub<T, SUB>(out + (vox * (unsigned)C + (unsigned)(cbase + sc * SUB)), d);
         }
     }
-    if constexpr (sizeof(T) == 2 && VDM_GNB_PACKED) {
+    if constexpr (sizeof(T) == 2) {
 #pragma unroll
         for (int j = 0; j < CH / 2; ++j) {
             gsum[2 * j] = gs2[j].x; gsum[2 * j + 1] = gs2[j].y;
@@ -1308,6 +1166,7 @@ struct Plan {
     int layout, cls_kind;                        // packed weights: VDM_CONV_VARIANT_GENERIC | _CLASS (of ClsKind cls_kind) | _KPACK
     int family;                                  // kernel: VDM_CONV_VARIANT_*
     int roll;                                    // generic family, 4x8x16 tile: rolling-z kernel
+    int nseg, zsteps;                            // rolling z: segments per tile column, z steps (tiles) per segment
     int tz, ty;                                  // spatial tile (TX = 16)
     int tiles;                                   // per-sample tiles of the GroupNorm partials [n][tiles][O][2]
     size_t packed_bytes;
@@ -1460,6 +1319,15 @@ static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed val
             // rolling-z kernel: one K-block, large grid: persistent walk up z; VDM4CDM_ROLL=0 switches it off (A/B)
             static const bool roll_on = getenv("VDM4CDM_ROLL") ? atoi(getenv("VDM4CDM_ROLL")) != 0 : true;
             p.roll = p.nkb == 1 && cdiv(p.Dz, 4) >= 4 && roll_on;
+            if (p.roll) {
+                const int ntz = cdiv(p.Dz, 4);
+                const long long ncols = (long long)p.N * cdiv(p.Dy, 8) * cdiv(p.Dx, 16) * p.nchunks;
+                int nseg = (int)((2LL * cu_count() + ncols - 1) / ncols);      // ~2 persistent workgroups per CU
+                if (nseg > ntz / 2) nseg = ntz / 2;                             // >= 2 steps per segment, or the walk saves nothing
+                if (nseg < 1) nseg = 1;
+                p.zsteps = cdiv(ntz, nseg);
+                p.nseg = cdiv(ntz, p.zsteps);
+            }
         }
     }
     p.tiles = cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16) * (p.cls_kind == CLS_UP_FWD && p.family == VDM_CONV_VARIANT_CLASS ? 8 : 1);
@@ -1596,7 +1464,6 @@ static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumul
 // launchers (defined in conv_fwd.hip / conv_cls.hip / conv_wgrad.hip / wgrad_thin.hip)
 int launch_fwd(const ConvArgs& a, const Plan& p, hipStream_t s);
 int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s);
-int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s);
 int run_cls(const vdm_conv_desc* d, const Plan& p, const void* x, const void* w, const float* bias, const void* res, void* out,
             hipStream_t s, float* gn_partials = nullptr);
 // weight gradient by its plan.  w / a: operands, dims and channel counts; slabs, tile counts and P are the launcher's to fill from the plan

@@ -10,12 +10,9 @@ namespace vdm {
 // 2h+1 = couts 16q + 8h .. +7 of every lane group q): twice the workgroups for the small grids of the deep levels, where a
 // workgroup's K-blocks run strictly one after the other and only co-resident workgroups overlap staging with MFMAs.
 // GNB: the GroupNorm+SiLU backward reduction is folded into the epilogue (dgrad launches that feed a GroupNorm: conv_epilogue_gnb).
-// GNP: the conv input is silu(gn(x)) of the raw tensor x (inference): GroupNorm + SiLU are applied to the staged image in LDS
-// (gn_prologue_inplace) instead of by a pass of their own.
-template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false>
+template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false>
 __global__ void __launch_bounds__(256, (TZ * TY <= 16 && NC <= 2) ? 3 : 2) conv_fwd_kernel(const ConvArgs a) {
     static_assert(!SPLIT || NC == 2, "half-chunk mode is the NC=2 kernel on NC=4 weights");
-    static_assert(!(GNB && GNP), "the prologue belongs to forward convs, the folded backward to dgrad convs");
     constexpr int NCW = SPLIT ? 4 : NC;
     using G = Geo<KS, STRIDE, TZ, TY>;
     constexpr int NV = G::NV, TAPS = G::TAPS;
@@ -29,13 +26,6 @@ __global__ void __launch_bounds__(256, (TZ * TY <= 16 && NC <= 2) ? 3 : 2) conv_
     VDM_STAMP(0);
 #endif
 
-#ifdef VDM_STAGGER
-    // experiment: the second workgroup a CU receives at launch (wave slot 1 of its SIMDs) starts half a tile period late, so that the
-    // two co-resident workgroups run in anti-phase (one stages / stores while the other is in its tap loop)
-    if (blockIdx.x < 2u * 256u && (__builtin_amdgcn_s_getreg((4 << 11) | 4) & 1)) {      // HW_REG_HW_ID bits [3:0] = wave slot
-        for (int i = 0; i < VDM_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
     int tx, ty, tz, n, chunk;
     decode_tile(a, (uint32_t)xcd_remap(blockIdx.x, gridDim.x), tx, ty, tz, n, chunk);
     const int oz0 = tz * TZ, oy0 = ty * TY, ox0 = tx * 16;
@@ -58,47 +48,28 @@ __global__ void __launch_bounds__(256, (TZ * TY <= 16 && NC <= 2) ? 3 : 2) conv_
     GnbRegs<T, NC, GNB ? NV : 1> gr;
     constexpr bool GNB_PRE = GNB && NC <= 2;
     float* gnb_tab = reinterpret_cast<float*>(lds + ((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES);      // (behind the GN scratch; read after the first barrier)
-    if constexpr (GNB && VDM_GNB_TABLE) gnb_consts_table(gnb_tab, a, n, e_cout0, tid);
-    if constexpr (GNB_PRE) gnb_issue<T, G, NC, NV, VDM_GNB_TABLE != 0>(gr, a, n, oz0, oy0, ox0, wave, lane, e_cout0, e_qstride);
+    if constexpr (GNB) gnb_consts_table(gnb_tab, a, n, e_cout0, tid);
+    if constexpr (GNB_PRE) gnb_issue<T, G, NC, NV, true>(gr, a, n, oz0, oy0, ox0, wave, lane, e_cout0, e_qstride);
     float badd[NC * 4];                                      // bias + conditioning bias of the lane's channels (latency hidden behind the taps)
     if constexpr (!GNB) load_badd<NC>(badd, a, n, e_cout0 + (lane >> 4) * e_qstride);
 
     for (int kb = 0; kb < a.nkb; ++kb) {
         if (kb) __syncthreads();
-        if constexpr (GNP)      // (the in-place GroupNorm prologue re-walks the chunks a wave staged: the chunk walk)
-            stage_halo_dma_chunks<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
-        else
-            stage_halo_dma<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane);
+        stage_halo_dma<T, G, UPS>(lds, x, a, n, oz0, oy0, ox0, kb, wave, lane);
         if (kb == 0) VDM_STAMP(6);
-        constexpr int IMG_ = ((G::HVOX + 15) / 16) * 1024;
-        float* gn_tab = reinterpret_cast<float*>(lds + IMG_ + GN_SCRATCH_BYTES);
-        if constexpr (GNP) {
-            if (kb == 0) {                                  // (behind the first DMA issue: the table is built while the halo is in flight)
-                gn_prologue_table(gn_tab, a, n, tid, 64 * G::NW);
-                __syncthreads();
-            }
-        }
         const uint4* wk = wbase + (size_t)kb * TAPS * NCW * 64;
         if constexpr (sizeof(T) == 2) {
             constexpr int WPD = WPipe<NC>::WPD;
             uint4 wf[WPD + 1][NC];
-            constexpr bool RR = VDM_ROWREUSE && KS == 3 && STRIDE == 1;     // activation rows reused across the dy taps
+            constexpr bool RR = KS == 3 && STRIDE == 1;    // activation rows reused across the dy taps
             if constexpr (RR) rr_prefetch_weights<NC, WPD, NCW>(wf, wk);
             else taps_prefetch_weights<TAPS, NC, WPD, NCW>(wf, wk);
             if (kb == 0) VDM_STAMP(1);
-            if constexpr (GNP) gn_prologue_inplace<T, G>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
             __syncthreads();
             if (kb == 0) VDM_STAMP(2);
-#ifdef VDM_TAP_PRIO
-            __builtin_amdgcn_s_setprio(VDM_TAP_PRIO);      // experiment: the wave in its tap loop wins instruction arbitration against the co-resident wave
-#endif
             if constexpr (RR) taps_rowreuse<T, G, NC, NV, WPD, NCW>(acc, lds, wk, wf, lanex);
             else taps_pipelined<T, G, NC, NV, WPD, NCW>(acc, lds, wk, wf, lanex);
-#ifdef VDM_TAP_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         } else {
-            if constexpr (GNP) gn_prologue_inplace<T, G>(lds, gn_tab, a, oz0, oy0, ox0, kb, wave, lane);
             __syncthreads();
             taps_rolled<T, G, NC, NV>(acc, lds, wk, lanex);
         }
@@ -109,7 +80,7 @@ __global__ void __launch_bounds__(256, (TZ * TY <= 16 && NC <= 2) ? 3 : 2) conv_
     const int tile = (tz * a.nty + ty) * a.ntx + tx;
     if constexpr (GNB) {
         static_assert(sizeof(T) == sizeof(TO), "the folded GroupNorm backward stores dyh in the activation dtype");
-        conv_epilogue_gnb<T, G, NC, NV, GNB_PRE, VDM_GNB_TABLE != 0>(acc, a, gr, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride, gnb_tab);
+        conv_epilogue_gnb<T, G, NC, NV, GNB_PRE, true>(acc, a, gr, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride, gnb_tab);
     } else
         conv_epilogue<T, TO, G, NC, NV>(acc, a, badd, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride);
 #ifdef VDM_TIMELINE
@@ -171,7 +142,7 @@ __global__ void __launch_bounds__(256, 2) conv_roll_kernel(const ConvArgs a) {
     const RowStager<T, G, 0> st(x, a, n, 0, oy0, ox0, 0, lane, 1, 0, 0, 0, a.Sz, a.Sy, a.Sx);
     float* gn_sm = reinterpret_cast<float*>(lds + R * SLICE);
     float* gnb_tab = reinterpret_cast<float*>(lds + R * SLICE + GN_SCRATCH_BYTES);
-    if constexpr (GNB && VDM_GNB_TABLE) gnb_consts_table(gnb_tab, a, n, e_cout0, tid);     // (one sample, one chunk per column: once; read behind the first barrier)
+    if constexpr (GNB) gnb_consts_table(gnb_tab, a, n, e_cout0, tid);     // (one sample, one chunk per column: once; read behind the first barrier)
     constexpr int WPD = WPipe<NC>::WPD;
 
     // slices are addressed by their position p = iz + 1 - 4 zs0 >= 0 in the column walk; slot = p mod 6
@@ -208,7 +179,7 @@ __global__ void __launch_bounds__(256, 2) conv_roll_kernel(const ConvArgs a) {
         }
         const int tile = (s * a.nty + ty) * a.ntx + tx;
         if constexpr (GNB)
-            conv_epilogue_gnb<T, G, NC, NV, false, VDM_GNB_TABLE != 0>(acc, a, gr, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride, gnb_tab);
+            conv_epilogue_gnb<T, G, NC, NV, false, true>(acc, a, gr, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride, gnb_tab);
         else
             conv_epilogue<T, T, G, NC, NV>(acc, a, badd, n, oz0, oy0, ox0, wave, lane, gn_sm, tile, e_cout0, e_qstride);
     }
@@ -404,15 +375,15 @@ __global__ void __launch_bounds__(256, GNB ? 2 : 4) conv_kpack_kernel(const Conv
                                         (tz * a.nty + ty) * a.ntx + tx, chunk * NC * 16, NC * 4);
 }
 
-template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false, bool GNP = false>
+template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, int TZ, int TY, bool SPLIT = false, bool GNB = false>
 static int launch_fwd_cfg(const ConvArgs& a0, hipStream_t s) {
     using G = Geo<KS, STRIDE, TZ, TY>;
     ConvArgs a = a0;
     if (SPLIT) a.nchunks *= 2;
     a.ntz = cdiv(a.Dz, TZ); a.nty = cdiv(a.Dy, TY); a.ntx = cdiv(a.Dx, 16);
     set_tile_divs(a);
-    const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES + (GNP ? GNP_TABLE_BYTES : 0) + (GNB ? GNB_TABLE_BYTES : 0);
-    auto kern = conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB, GNP>;
+    const size_t lds = (size_t)((G::HVOX + 15) / 16) * 1024 + GN_SCRATCH_BYTES + (GNB ? GNB_TABLE_BYTES : 0);
+    auto kern = conv_fwd_kernel<T, TO, KS, STRIDE, UPS, NC, TZ, TY, SPLIT, GNB>;
     static unsigned long long lds_done = 0;
     {
         int e = set_lds(kern, lds, lds_done);
@@ -430,16 +401,11 @@ static int launch_fwd_cfg(const ConvArgs& a0, hipStream_t s) {
 
 // rolling-z kernel: bf16, one K-block, 3x3x3 stride 1, bf16 output, 4x8x16 steps (Plan::roll)
 template <typename T, int NC, bool GNB>
-static int launch_roll(const ConvArgs& a0, hipStream_t s) {
+static int launch_roll(const ConvArgs& a0, const Plan& p, hipStream_t s) {
     using G = Geo<3, 1, 4, 8>;
     ConvArgs a = a0;
     a.ntz = cdiv(a.Dz, G::TZ); a.nty = cdiv(a.Dy, G::TY); a.ntx = cdiv(a.Dx, 16);
-    const long long ncols = (long long)a.N * a.nty * a.ntx * a.nchunks;
-    int nseg = (int)((2LL * cu_count() + ncols - 1) / ncols);          // ~2 persistent workgroups per CU
-    if (nseg > a.ntz / 2) nseg = a.ntz / 2;                             // >= 2 steps per segment, or the walk saves nothing
-    if (nseg < 1) nseg = 1;
-    a.zsteps = cdiv(a.ntz, nseg);
-    a.nseg = cdiv(a.ntz, a.zsteps);
+    a.nseg = p.nseg; a.zsteps = p.zsteps;
     a.fdx = make_fastdiv((uint32_t)a.ntx); a.fdy = make_fastdiv((uint32_t)a.nty); a.fdz = make_fastdiv((uint32_t)a.nseg);
     a.fdn = make_fastdiv((uint32_t)a.N);
     const size_t lds = (size_t)6 * G::HY * G::HX * 64 + GN_SCRATCH_BYTES + (GNB ? GNB_TABLE_BYTES : 0);
@@ -449,7 +415,7 @@ static int launch_roll(const ConvArgs& a0, hipStream_t s) {
         int e = set_lds(kern, lds, lds_done);
         if (e) return e;
     }
-    const long long nwg = ncols * a.nseg;
+    const long long nwg = (long long)a.N * a.nty * a.ntx * a.nchunks * a.nseg;
     if (nwg > 0x7fffffffLL) { set_error("conv: grid too large"); return VDM_ERR_ARG; }
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds, s, a);
     VDM_LAUNCH_CHECK("conv_roll_kernel");
@@ -477,7 +443,7 @@ static int launch_ksplit(const ConvArgs& a0, hipStream_t s) {
 }
 
 // plan -> template instantiation.  Every run-time choice is plan_of()'s; the `if constexpr` guards only bound the set of built kernels.
-template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, bool GNB = false, bool GNP = false>
+template <typename T, typename TO, int KS, int STRIDE, int UPS, int NC, bool GNB = false>
 static int launch_fwd_geo(const ConvArgs& a, const Plan& p, hipStream_t s) {
     const int tz = p.tz, ty = p.ty;
     if constexpr (STRIDE == 2)
@@ -485,30 +451,29 @@ static int launch_fwd_geo(const ConvArgs& a, const Plan& p, hipStream_t s) {
     else if constexpr (KS == 3) {
         if constexpr (NC == 4 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2) {
             if (p.family == VDM_CONV_VARIANT_KSPLIT) {
-                if constexpr (GNP) { set_error("conv_fwd_gn: the K-split kernel has no GroupNorm prologue (vdm_conv_fwd_gn_supported)"); return VDM_ERR_UNSUPPORTED; }
-                else return ty == 4 ? launch_ksplit<T, TO, 4, 4, GNB>(a, s) : launch_ksplit<T, TO, 4, 8, GNB>(a, s);
+                return ty == 4 ? launch_ksplit<T, TO, 4, 4, GNB>(a, s) : launch_ksplit<T, TO, 4, 8, GNB>(a, s);
             }
             if (p.family == VDM_CONV_VARIANT_SPLIT) {
-                if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 4, true, GNB, GNP>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 8, true, GNB, GNP>(a, s);
-                return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 2, 8, true, GNB, GNP>(a, s);
+                if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 4, true, GNB>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 1, 8, true, GNB>(a, s);
+                return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, 2, 2, 8, true, GNB>(a, s);
             }
         }
-        if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4, false, GNB, GNP>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 8, false, GNB, GNP>(a, s);
-        if (tz == 2) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 8, false, GNB, GNP>(a, s);
-        if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2 && !GNP) {      // (the prologue runs on the plain 4x8x16 kernel)
-            if (p.roll) return launch_roll<T, NC, GNB>(a, s);
+        if (tz == 1) return ty == 4 ? launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 4, false, GNB>(a, s) : launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 1, 8, false, GNB>(a, s);
+        if (tz == 2) return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 2, 8, false, GNB>(a, s);
+        if constexpr (STRIDE == 1 && UPS == 0 && sizeof(TO) == 2 && sizeof(T) == 2 && NC == 2) {
+            if (p.roll) return launch_roll<T, NC, GNB>(a, p, s);
         }
-        return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP>(a, s);
+        return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB>(a, s);
     } else
-        return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB, GNP>(a, s);
+        return launch_fwd_cfg<T, TO, KS, STRIDE, UPS, NC, 4, 8, false, GNB>(a, s);
 }
 
-template <typename T, typename TO, int KS, int STRIDE, int UPS, bool GNB = false, bool GNP = false>
+template <typename T, typename TO, int KS, int STRIDE, int UPS, bool GNB = false>
 static int launch_fwd_nc(const ConvArgs& a, const Plan& p, hipStream_t s) {
     switch (p.nc) {
-        case 1: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 1, GNB, GNP>(a, p, s);
-        case 2: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 2, GNB, GNP>(a, p, s);
-        default: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 4, GNB, GNP>(a, p, s);
+        case 1: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 1, GNB>(a, p, s);
+        case 2: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 2, GNB>(a, p, s);
+        default: return launch_fwd_geo<T, TO, KS, STRIDE, UPS, 4, GNB>(a, p, s);
     }
 }
 
@@ -552,12 +517,6 @@ int launch_fwd_gnb(const ConvArgs& a, const Plan& p, hipStream_t s) {
     if (p.family == VDM_CONV_VARIANT_KPACK) return p.nc == 1 ? launch_kpack<1, true>(a, s) : launch_kpack<2, true>(a, s);
     if (p.dtype == VDM_F32) return launch_fwd_nc<float, float, 3, 1, 0, true>(a, p, s);
     return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, true>(a, p, s);
-}
-
-// forward 3x3x3 stride-1 conv of y = silu(gn(x)) with GroupNorm + SiLU applied to the staged image (ConvArgs::gstats ... set; bf16)
-int launch_fwd_gnp(const ConvArgs& a, const Plan& p, hipStream_t s) {
-    if (p.out_f32) return launch_fwd_geo<bf16_t, float, 3, 1, 0, 1, false, true>(a, p, s);
-    return launch_fwd_nc<bf16_t, bf16_t, 3, 1, 0, false, true>(a, p, s);
 }
 
 }  // namespace vdm

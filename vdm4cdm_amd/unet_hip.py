@@ -22,13 +22,6 @@ FUSED_GN = os.environ.get("VDM4CDM_FUSED_GN", "1") != "0"
 FUSED_GNB = FUSED_GN and os.environ.get("VDM4CDM_FUSED_GNB", "1") != "0"
 # the 1x1x1 skip conv of a ResNetBlock rides along with norm1's GroupNorm passes where csrc/gn_skip.hip has a kernel (bf16, narrow layers)
 FUSED_SKIP = os.environ.get("VDM4CDM_FUSED_SKIP", "1") != "0"
-# inference: norm2's GroupNorm + SiLU applied inside conv2 (to the staged halo image) instead of by a pass of its own.  Measured: the
-# VALU work on the 2.1x halo costs the conv what the 5 TB/s pass cost - off by default
-# "0" (default): nowhere; "deep": only at the levels of <= 32^3 voxels; "1": everywhere.  Round 4, same box, 300 sampling steps at 128^3:
-# 2.42 / 2.43 / 2.46 ms per step for 0 / deep / 1 - the fold does not pay at any level (the level-3 convs run the K-split kernel, which
-# has no prologue: "deep" reaches two launches per step)
-GN_PROLOGUE = os.environ.get("VDM4CDM_GN_PROLOGUE", "0")
-GN_PROLOGUE_MAX_VOXELS = 32 ** 3
 
 class SideStream:
     """Weight-gradient kernels run on a side HIP stream: their results are needed only by the optimiser, so they overlap
@@ -147,9 +140,7 @@ class _Res:
             a1 = ops.gn_silu_fwd(x1, x2, G, st1, P(n + ".norm1.weight"), P(n + ".norm1.bias"))
         h = self.conv1.fwd(a1, P(n + ".conv1.bias"), table[:, i.table_off:i.table_off + i.cout], gn=FUSED_GN)
         st2 = ops.gn_stats(h, None, G, chsum=save and FUSED_GNB)
-        inside = (GN_PROLOGUE != "0" and not save and p == 0.0 and (GN_PROLOGUE == "1" or h[0, ..., 0].numel() <= GN_PROLOGUE_MAX_VOXELS)
-                  and self.conv2.gn_in_ok(h))
-        a2 = None if inside else ops.gn_silu_fwd(h, None, G, st2, P(n + ".norm2.weight"), P(n + ".norm2.bias"), p, seed, want_mask=save and FUSED_GNB)
+        a2 = ops.gn_silu_fwd(h, None, G, st2, P(n + ".norm2.weight"), P(n + ".norm2.bias"), p, seed, want_mask=save and FUSED_GNB)
         if ride:
             pass
         elif self.skip1 is not None:
@@ -159,10 +150,7 @@ class _Res:
                 s.record_stream(torch.cuda.current_stream())
         else:
             s = x1
-        if inside:
-            out = self.conv2.fwd(h, P(n + ".conv2.bias"), None, s, gn=FUSED_GN, gn_in=(G, st2, P(n + ".norm2.weight"), P(n + ".norm2.bias")))
-        else:
-            out = self.conv2.fwd(a2, P(n + ".conv2.bias"), None, s, gn=FUSED_GN)     # (every block output feeds a GroupNorm)
+        out = self.conv2.fwd(a2, P(n + ".conv2.bias"), None, s, gn=FUSED_GN)     # (every block output feeds a GroupNorm)
         if save:
             self.saved = (x1, x2, st1, a1, h, st2, a2, p, seed, a2.keep_mask)
         return out
