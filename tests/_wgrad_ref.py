@@ -97,7 +97,7 @@ def mfma_shape(bf16, fp32_exact):
 
 def _slab_reduce(nslabs):
     """wgrad_reduce_direct_kernel (<= 32 slabs: one thread adds them in turn) or wgrad_reduce_kernel (four groups add every fourth
-    slab in turn, then the four group sums are added in turn).  The larger of the two where either may run (VDM4CDM_GROUPED_REDUCE)."""
+    slab in turn, then the four group sums are added in turn).  The larger of the two where either may run (VDM4CDM_EXPERIMENT=grouped_reduce)."""
     grouped = cdiv(nslabs, 4) + 4
     return grouped if nslabs > 32 else max(nslabs, grouped)
 

@@ -144,7 +144,7 @@ def _reseed(seed=9):
 
 @pytest.mark.parametrize("K", [2, 3])
 def test_fused_head_equals_unfused_head_fp32(K, monkeypatch):
-    """The fused head (vdm_diffuse_pack_fields) and VDM4CDM_FUSED_HEAD=0 (randn -> diffuse -> vdm_pack_fields) from the same generator
+    """The fused head (vdm_diffuse_pack_fields) and VDM4CDM_EXPERIMENT=fused_head=0 (randn -> diffuse -> vdm_pack_fields) from the same generator
     state: the same loss, ELBO parts and parameter gradient, bit for bit."""
     import vdm4cdm_amd.vdm_model as vm
     net = make_net(K, dropout=0.1)

@@ -864,7 +864,7 @@ THIN_CASES = [
 @pytest.mark.parametrize("case", THIN_CASES, ids=[c[0] for c in THIN_CASES])
 def test_wgrad_thin_side(case):
     """Weight gradient of conv_in / conv_out shaped convs (one side <= 2 channels: csrc/wgrad_thin.hip) against torch.autograd of the
-    reference conv; bf16 storage: 2^-7 of max|dW|; bit-reproducible; the generic kernel (VDM4CDM_NO_THIN_WGRAD) agrees."""
+    reference conv; bf16 storage: 2^-7 of max|dW|; bit-reproducible; the generic kernel (VDM4CDM_EXPERIMENT=thin_wgrad=0) agrees."""
     dtype = torch.bfloat16
     ops, conv, x, w, xd = _conv_setup(case, dtype, seed=30)
     name, N, (D, H, W), cin, cout, ks, stride, ups, circ = case

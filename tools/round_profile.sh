@@ -37,8 +37,8 @@ python tools/sampler_profile.py --steps 200 > "$out/${tag}_sampler_plain.json" 2
 cat "$out/${tag}_sampler_plain.json"
 # phase stamps of the weight-gradient kernels (diagnostic build), tap-split kernel next to the row-resident rolling kernel
 if [ -f vdm4cdm_amd/libvdm4cdm_hip_timeline.so ]; then
-  ( for v in 0 1; do VDM4CDM_WGRAD_ROWS=$v VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_32_32; done
-    VDM4CDM_WGRAD_WGS=256 VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_32_32
+  ( for v in 0 1; do VDM4CDM_EXPERIMENT=wgrad_rows=$v VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_32_32; done
+    VDM4CDM_EXPERIMENT=wgrad_wgs=256 VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_32_32
     VDM4CDM_LIB=$PWD/vdm4cdm_amd/libvdm4cdm_hip_timeline.so python tools/wgrad_phases.py --shape L0_64_32 ) 2>&1 | grep -v amdgpu.ids > "$out/${tag}_wgrad_phases.txt"
 fi
 python bench.py --config c2 --steps 40 --warmup 5 --full --no-cpu-baseline --sample-steps 0 > "$out/${tag}_bench_c2.json" 2>/dev/null

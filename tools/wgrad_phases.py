@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Phase times of the 3^3 weight-gradient kernels (csrc/conv_wgrad.hip) from the stamped diagnostic build:
     make -C vdm4cdm_amd/csrc timeline
-    VDM4CDM_LIB=vdm4cdm_amd/libvdm4cdm_hip_timeline.so [VDM4CDM_WGRAD_ROWS=0|1] python tools/wgrad_phases.py [--shape L0_32_32] [--stride 1|2]
+    VDM4CDM_LIB=vdm4cdm_amd/libvdm4cdm_hip_timeline.so [VDM4CDM_EXPERIMENT=wgrad_rows=0|1] python tools/wgrad_phases.py [--shape L0_32_32] [--stride 1|2]
 Every wave sums the s_memrealtime ticks (100 MHz) it spends per phase over the tiles of its persistent workgroup; printed per tile."""
 import argparse
 import os
@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vdm4cdm_amd import _lib, hip_ops as ops  # noqa: E402
+from vdm4cdm_amd import _experiment, _lib, hip_ops as ops  # noqa: E402
 
 SHAPES = {"L0_32_32": (128, 32, 32), "L0_64_32": (128, 64, 32), "L1_64_64": (64, 64, 64), "L2_128_128": (32, 128, 128)}
 
@@ -57,8 +57,8 @@ def main():
     life = (s[:, :, 7] - s[:, :, 6]) / 100.0
     names = ["wait: other waves still read the previous tile", "tile decode + LDS-DMA issue", "DMA landed (vmcnt 0 + barrier)",
              "operand reads + MFMAs", "bias column sums", "slab write (once)"]
-    rows = os.environ.get("VDM4CDM_WGRAD_ROWS", "1")
-    print(f"{args.shape} stride {args.stride} N={args.n} WGRAD_ROWS={rows} kernel {info.kernel} tile {info.tz}x{info.ty}x16: {nwg} workgroups x {per_wg:.1f} tiles, launch {e0.elapsed_time(e1) * 1e3:.1f} us "
+    rows = _experiment.get("wgrad_rows")
+    print(f"{args.shape} stride {args.stride} N={args.n} wgrad_rows={rows} kernel {info.kernel} tile {info.tz}x{info.ty}x16: {nwg} workgroups x {per_wg:.1f} tiles, launch {e0.elapsed_time(e1) * 1e3:.1f} us "
           f"(stamped build, incl. the slab reduce), workgroup life {life.mean():.1f} us")
     for k, nm in enumerate(names):
         v = us[:, :, k].reshape(-1)

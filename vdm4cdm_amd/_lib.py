@@ -8,6 +8,8 @@ import ctypes as C
 import os
 import subprocess
 
+from . import _experiment            # noqa: F401  validates VDM4CDM_EXPERIMENT before the library (which reads it leniently) is loaded
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VDM4CDM_LIB: load another build of the same library (tools/conv_timeline.py uses the stamped diagnostic build)
 # VDM4CDM_FP32_EXACT=1: fp32 storage computes with the exact fp32 MFMA (1/16 of the bf16 rate) instead of three bf16 MFMAs per product

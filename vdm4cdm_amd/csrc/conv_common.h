@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "experiment.h"
 
 namespace vdm {
 
@@ -1223,17 +1224,15 @@ static void small_grid_tile(Plan& p) {
 // weights; bf16 3x3x3 stride 1, not the up-sampling conv)
 static bool uses_split(const Plan& p) {
     const long long wgs = (long long)p.nchunks * p.N * cdiv(p.Dz, p.tz) * cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16);
-    static const bool split_on = getenv("VDM4CDM_NO_SPLIT") == nullptr;
-    return p.tz <= 2 && wgs < 2LL * cu_count() && p.O % 64 == 0 && split_on;
+    return p.tz <= 2 && wgs < 2LL * cu_count() && p.O % 64 == 0 && experiment().split;
 }
 
 // K-split kernel of the deepest levels (conv_fwd.hip, conv_ksplit_kernel): bf16 3x3x3 stride-1 convs with >= 4 K-blocks and 64-cout
 // chunks whose grid is small enough for small_grid_tile() to choose a 1 x ty x 16 tile (level 3 of the 128^3 network), which the
 // K-split kernel keeps.  Not the 2x8x16 grids (level 2: measured SLOWER there - 0.078 vs 0.054 ms at batch 2 - one workgroup per CU
-// loses more than the saved weight traffic gains).  VDM4CDM_KSPLIT=0 switches it off (A/B).
+// loses more than the saved weight traffic gains).  VDM4CDM_EXPERIMENT=ksplit=0 switches it off (A/B).
 static bool uses_ksplit(const Plan& p) {
-    static const bool on = getenv("VDM4CDM_KSPLIT") ? atoi(getenv("VDM4CDM_KSPLIT")) > 0 : true;
-    return on && p.nkb >= 4 && p.O % 64 == 0 && p.tz == 1;
+    return experiment().ksplit && p.nkb >= 4 && p.O % 64 == 0 && p.tz == 1;
 }
 
 // ---- class-conv tables -----------------------------------------------------------------------
@@ -1282,8 +1281,6 @@ static void build_cls(int kind, ClsTable& tab, ClsMasks& masks) {
     }
 }
 
-static bool kpack_enabled() { static const bool on = getenv("VDM4CDM_NO_KPACK") == nullptr; return on; }
-
 static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed validate()
     Plan p{};
     p.taps = d->ksize * d->ksize * d->ksize;
@@ -1304,7 +1301,7 @@ static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed val
         p.cls_kind = d->upsample ? (dgrad ? CLS_UP_DGRAD : CLS_UP_FWD) : CLS_S2_DGRAD;
         if (d->upsample) { p.Dz /= 2; p.Dy /= 2; p.Dx /= 2; }
         slots = (size_t)p.nkb * 64;                         // 64 (class, entry) slots
-    } else if (bf16io && p.ks == 3 && p.stride == 1 && p.K <= 8 && p.O <= 32 && kpack_enabled()) {
+    } else if (bf16io && p.ks == 3 && p.stride == 1 && p.K <= 8 && p.O <= 32 && experiment().kpack) {
         p.layout = p.family = VDM_CONV_VARIANT_KPACK;      // tap-packed kernel, 4x8x16
         slots = 7;                                          // 7 groups of 4 taps
     } else if (p.stride == 2) {
@@ -1316,9 +1313,8 @@ static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed val
             else if (uses_split(p)) p.family = VDM_CONV_VARIANT_SPLIT;
         }
         if (bf16io && p.nc == 2 && p.tz == 4) {            // (NC = 4 needs > 128 registers per wave: its accumulators alone are 64)
-            // rolling-z kernel: one K-block, large grid: persistent walk up z; VDM4CDM_ROLL=0 switches it off (A/B)
-            static const bool roll_on = getenv("VDM4CDM_ROLL") ? atoi(getenv("VDM4CDM_ROLL")) != 0 : true;
-            p.roll = p.nkb == 1 && cdiv(p.Dz, 4) >= 4 && roll_on;
+            // rolling-z kernel: one K-block, large grid: persistent walk up z; VDM4CDM_EXPERIMENT=roll=0 switches it off (A/B)
+            p.roll = p.nkb == 1 && cdiv(p.Dz, 4) >= 4 && experiment().roll;
             if (p.roll) {
                 const int ntz = cdiv(p.Dz, 4);
                 const long long ncols = (long long)p.N * cdiv(p.Dy, 8) * cdiv(p.Dx, 16) * p.nchunks;
@@ -1344,7 +1340,7 @@ static void fill_dims(ConvArgs& a, const vdm_conv_desc* d) {
 
 // ---------------------------------------------------------------------------------------------
 // The weight gradient's plan.  plan_wgrad() and the helpers right above it are the only place that decides the kernel, its tile, the
-// number of partial slabs and the workspace of a weight gradient - and the only readers of the VDM4CDM_* switches of that direction.
+// number of partial slabs and the workspace of a weight gradient - and the only readers of the switches of that direction (experiment.h).
 // vdm_conv_wgrad, the workspace / plan queries and the launchers (conv_wgrad.hip, wgrad_thin.hip) read the plan.
 // ---------------------------------------------------------------------------------------------
 struct ThinArgs {            // wgrad_thin.hip
@@ -1375,19 +1371,8 @@ struct WgradPlan {
     size_t workspace_bytes;
 };
 
-// the switches (experiments, A/B runs; read once per process)
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-// persistent workgroups of a weight-gradient launch over all (cout, cin) block pairs (~2 per CU)
-static int wgrad_wgs() { static const int v = env_int("VDM4CDM_WGRAD_WGS", 512); return v > 0 ? v : 512; }
 // persistent workgroups of the thin-side kernel (4 waves each, one chunk per wave in flight ahead of the one it consumes)
 constexpr int THIN_WORKGROUPS = 512;
-static bool wgrad_thin_enabled() { static const bool on = getenv("VDM4CDM_NO_THIN_WGRAD") == nullptr; return on; }
-// VDM4CDM_WGRAD_ROWS=0: the tap-split kernel also for the full bf16 3^3 stride-1 blocks
-static bool wgrad_rows_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROWS", 1) != 0; return on; }
-// VDM4CDM_WGRAD_ROLL=0: no rolling z window - the persistent workgroups of the rows kernel walk scattered tiles, not column segments
-static bool wgrad_roll_enabled() { static const bool on = env_int("VDM4CDM_WGRAD_ROLL", 1) != 0; return on; }
-// VDM4CDM_GROUPED_REDUCE: the grouped slab reduce also for few slabs (same result, other launch shape)
-static bool wgrad_grouped_only() { static const bool on = getenv("VDM4CDM_GROUPED_REDUCE") != nullptr; return on; }
 
 // thin-side kernel (wgrad_thin.hip): `cdense` channels on the dense side; also the plan of vdm_gn_bwd_apply_wgrad_thin, which has no descriptor
 static WgradPlan plan_wgrad_thin(int kernel, int n, int od, int oh, int ow, int cdense) {
@@ -1404,7 +1389,7 @@ static WgradPlan plan_wgrad_thin(int kernel, int n, int od, int oh, int ow, int 
 static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumulate) {      // d has passed validate()
     const bool bf16 = d->dtype == VDM_BF16, k3s1 = d->ksize == 3 && d->stride == 1 && !d->upsample;
     // conv_in / conv_out: one side has <= 2 channels (written, not accumulated; circular padding wraps inside one 32-voxel chunk: ow >= 17)
-    if (bf16 && k3s1 && !accumulate && wgrad_thin_enabled() && !(d->pad_mode == VDM_PAD_CIRCULAR && d->ow < 17)) {
+    if (bf16 && k3s1 && !accumulate && experiment().thin_wgrad && !(d->pad_mode == VDM_PAD_CIRCULAR && d->ow < 17)) {
         const auto dense_ok = [](int c) { return c == 16 || c == 32 || c == 64; };
         if (d->cin <= 2 && dense_ok(d->cout)) return plan_wgrad_thin(VDM_WGRAD_THIN_IN, d->n, d->od, d->oh, d->ow, d->cout);
         if (d->cout == 1 && !want_bias && dense_ok(d->cin)) return plan_wgrad_thin(VDM_WGRAD_THIN_OUT, d->n, d->od, d->oh, d->ow, d->cin);
@@ -1432,16 +1417,16 @@ static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumul
         p.tz = 2; p.ty = 8;
         if (bf16 && d->cin <= 16) p.ntb = 1;     // 64-byte blocks with a single real 16-channel tile
         else if (bf16 && d->cout <= 16) p.nta = 1;
-        else if (bf16 && wgrad_rows_enabled()) p.kernel = VDM_WGRAD_ROWS;
+        else if (bf16 && experiment().wgrad_rows) p.kernel = VDM_WGRAD_ROWS;
     }
     p.ntz = cdiv(Dz, p.tz); p.nty = cdiv(Dy, p.ty); p.ntx = cdiv(Dx, 16);
     // validate() bounds a sample's voxels by 2^32 / 4 channels; the batch (<= 2^20) on top of that must still fit the kernels' int tile index
     const long long ntiles = (long long)d->n * p.ntz * p.nty * p.ntx;
     p.ntiles = (int)(ntiles < 0x7fffffffLL ? ntiles : 0x7fffffffLL);
-    p.P = wgrad_wgs() / p.npairs;
+    p.P = experiment().wgrad_wgs / p.npairs;
     if (p.P < 1) p.P = 1;
     if (p.P > p.ntiles) p.P = p.ntiles;
-    if (p.kernel == VDM_WGRAD_ROWS && wgrad_roll_enabled()) {
+    if (p.kernel == VDM_WGRAD_ROWS && experiment().wgrad_roll) {
         const long long ncols = (long long)d->n * p.nty * p.ntx;
         int nseg = (int)(p.P / ncols);                          // P = the workgroups this pair may use
         if (nseg > p.ntz / 2) nseg = p.ntz / 2;                 // >= 2 steps per segment, or the walk saves nothing
@@ -1455,7 +1440,7 @@ static WgradPlan plan_wgrad(const vdm_conv_desc* d, bool want_bias, bool accumul
         }
     }
     p.grid = p.npairs * p.P;
-    p.grouped = p.P * p.per_wg > 32 || wgrad_grouped_only();
+    p.grouped = p.P * p.per_wg > 32 || experiment().grouped_reduce;
     p.slab_bytes = (size_t)p.npairs * p.P * slots * p.CL * p.CL * sizeof(float);
     p.workspace_bytes = p.slab_bytes + (size_t)p.ncb * bias_rows * p.P * p.CL * sizeof(float);
     return p;

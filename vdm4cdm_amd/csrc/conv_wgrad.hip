@@ -523,8 +523,8 @@ __global__ void __launch_bounds__(256) wgrad_cls_reduce_kernel(const float* __re
 // timing ablation (tools/ablate_step.sh): the slab reduce is NOT launched - weight gradients are garbage.  Says so, loudly, once.
 static bool ablate_reduce() {
     static const bool on = [] {
-        const bool v = getenv("VDM4CDM_ABLATE_REDUCE") != nullptr;
-        if (v) fprintf(stderr, "\n*** libvdm4cdm_hip: VDM4CDM_ABLATE_REDUCE is set - weight-gradient slab reduces are SKIPPED, gradients are WRONG "
+        const bool v = experiment().ablate_reduce != 0;
+        if (v) fprintf(stderr, "\n*** libvdm4cdm_hip: VDM4CDM_EXPERIMENT=ablate_reduce is set - weight-gradient slab reduces are SKIPPED, gradients are WRONG "
                                "(timing ablation only; unset it for any real run) ***\n\n");
         return v;
     }();

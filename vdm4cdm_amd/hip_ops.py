@@ -8,17 +8,13 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _experiment, _lib
 from ._lib import CondMlp, ConvDesc, GnFold, PACK_DGRAD, PACK_FWD, VDM_BF16, VDM_F32, check
 
 GN_EPS = 1e-5
 # timing ablations (tools/ablate_step.sh): kernels named here are NOT launched (wrong results - only bench.py timing runs set this)
-import os as _os
-ABLATE = set(filter(None, _os.environ.get("VDM4CDM_ABLATE", "").split(",")))
-if ABLATE or "VDM4CDM_ABLATE_REDUCE" in _os.environ:
-    import sys as _sys
-    print(f"\n*** vdm4cdm_amd.hip_ops: VDM4CDM_ABLATE={sorted(ABLATE)} / VDM4CDM_ABLATE_REDUCE set - kernels are SKIPPED and results are WRONG "
-          "(timing ablations of tools/ablate_step.sh only; Trainer.fit refuses to run) ***\n", file=_sys.stderr, flush=True)
+ABLATE = set(_experiment.get("ablate"))
+FUSED_TAIL = bool(_experiment.get("fused_tail"))      # gn_tail_ok (fused_tail=0: separate apply pass and weight gradient, for A/B timing)
 
 
 class KernelProfiler:
@@ -453,7 +449,7 @@ def gn_silu_bwd(x1, x2, groups, stats, gamma, beta, dy, dgamma, dbeta, add1=None
 def gn_tail_ok(conv_in, x):
     """Can the last GroupNorm backward + conv_in's weight gradient run as one pass (gn_bwd_fused(..., tail=...))?  Where the plan of
     conv_in's weight gradient (with bias, written) is the thin-input kernel, at batch <= 16."""
-    if conv_in.cout != x.shape[-1] or x.shape[0] > 16 or _os.environ.get("VDM4CDM_FUSED_TAIL", "1") == "0":
+    if conv_in.cout != x.shape[-1] or x.shape[0] > 16 or not FUSED_TAIL:
         return False
     info = _lib.WgradPlanInfo()
     n, od, oh, ow, _ = x.shape

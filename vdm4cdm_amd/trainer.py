@@ -351,9 +351,8 @@ class Trainer:
         use_hip = dev_type == "cuda" and getattr(model.model.score_model, "backend", "") == "hip"
         graphed = self.graph_step and use_hip and self.world == 1 and getattr(model.model, "noise_schedule", "") == "fixed_linear"
         if use_hip:
-            from . import hip_ops as ops
-            if ops.ABLATE or "VDM4CDM_ABLATE_REDUCE" in os.environ:      # timing switches of tools/ablate_step.sh skip kernels: never train with them
-                raise RuntimeError(f"VDM4CDM_ABLATE={sorted(ops.ABLATE)} is set: kernels are skipped and gradients are garbage - unset it")
+            from . import _experiment
+            _experiment.refuse_for_training()      # timing switches of tools/ablate_step.sh skip kernels: never train with them
         if _accepts(model.configure_optimizers, "capturable"):
             opt = model.configure_optimizers(capturable=graphed)
         else:                                                # (a user model with the reference's zero-argument signature)

@@ -13,15 +13,17 @@ import torch
 import os
 
 from . import hip_ops as ops
+from ._experiment import get
 from .hip_ops import Conv
 
-# GroupNorm statistics from the producing conv's epilogue (VDM4CDM_FUSED_GN=0: separate gn_stats passes, for A/B timing)
-FUSED_GN = os.environ.get("VDM4CDM_FUSED_GN", "1") != "0"
-# GroupNorm backward reduction folded into the producing dgrad conv's epilogue (VDM4CDM_FUSED_GNB=0: separate reduce pass with
-# float atomics, for A/B timing).  Needs the forward partials (FUSED_GN) for the analytic conditioning-table gradient.
-FUSED_GNB = FUSED_GN and os.environ.get("VDM4CDM_FUSED_GNB", "1") != "0"
+# The switches below are keys of VDM4CDM_EXPERIMENT (_experiment.py), for A/B timing.
+# GroupNorm statistics from the producing conv's epilogue (fused_gn=0: separate gn_stats passes)
+FUSED_GN = bool(get("fused_gn"))
+# GroupNorm backward reduction folded into the producing dgrad conv's epilogue (fused_gnb=0: separate gn_dyh and channel_dot_sums passes,
+# fixed summation order too).  Needs the forward partials (fused_gn) for the analytic conditioning-table gradient: fused_gn=0 forces it off.
+FUSED_GNB = bool(get("fused_gnb"))
 # the 1x1x1 skip conv of a ResNetBlock rides along with norm1's GroupNorm passes where csrc/gn_skip.hip has a kernel (bf16, narrow layers)
-FUSED_SKIP = os.environ.get("VDM4CDM_FUSED_SKIP", "1") != "0"
+FUSED_SKIP = bool(get("fused_skip"))
 
 class SideStream:
     """Weight-gradient kernels run on a side HIP stream: their results are needed only by the optimiser, so they overlap
@@ -32,7 +34,7 @@ class SideStream:
         self.enabled = enabled and torch.cuda.is_available()
         self.side = torch.cuda.Stream(device=device) if self.enabled else None
         # a second, independent side stream (the skip-path input gradients must not queue behind the weight gradients)
-        self.second = SideStream(device, enabled and os.environ.get("VDM4CDM_SKIP_DGRAD_STREAM", "1") != "0", with_second=False) if with_second else None
+        self.second = SideStream(device, enabled and bool(get("skip_dgrad_stream")), with_second=False) if with_second else None
 
     def run(self, fn, *tensors):
         if not self.enabled:
@@ -86,7 +88,7 @@ class DeferredSide:
 
 
 # weight gradients of the up path's first N levels are deferred until the main stream starts the next level (0: launch immediately)
-DEFER_WGRAD_LEVELS = int(os.environ.get("VDM4CDM_DEFER_WGRAD_LEVELS", "1"))
+DEFER_WGRAD_LEVELS = get("defer_wgrad_levels")
 
 
 class _Res:
@@ -344,10 +346,10 @@ class HipUNet:
             out.extend(self.attn.convs())
         return out
 
-    def pack_weights(self, flat, dtype, need_dgrad, overlap=False):
+    def pack_weights(self, flat, dtype, need_dgrad):
         """Re-pack master fp32 weights into MFMA fragment order when the parameters changed (one launch on the current stream, ordered
-        behind the optimizer step that changed them).  `overlap` is accepted and ignored: running the launch on a stream of its own next
-        to the head of the next step bought 0.05 ms and cost a cross-stream use-after-free and a broken capture (rounds 3-4); deleted."""
+        behind the optimizer step that changed them.  Running the launch on a stream of its own next to the head of the next step
+        bought 0.05 ms and cost a cross-stream use-after-free and a broken capture (rounds 3-4); deleted)."""
         # flat._version alone is NOT enough: fused optimizers (torch._fused_adamw_) update the parameters without bumping the
         # version counter.  net.weights_epoch is bumped by every backward pass of this executor (an optimizer step follows) and by
         # CUNet.mark_weights_dirty() (the optimizer post-step hook LightVDM.configure_optimizers installs).
@@ -376,7 +378,7 @@ class HipUNet:
 
     def _side_stream(self, device):
         if self._ss is None or (self._ss.enabled and self._ss.side.device != device):
-            self._ss = SideStream(device, enabled=os.environ.get("VDM4CDM_WGRAD_STREAM", "1") != "0")
+            self._ss = SideStream(device, enabled=bool(get("wgrad_stream")))
         return self._ss
 
     # ---------------------------------------------------------------------------------------

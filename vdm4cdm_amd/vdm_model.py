@@ -20,13 +20,12 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import os
-
+from . import _experiment
 from .sampling import ChainNoise, ddnm_lengths, ddnm_sample, ddnm_schedule, hip_ddnm_sampler, hip_graph_sampler  # noqa: F401
 
 DATA_NOISE = 1.0e-3
-# Fused head of the HIP training step (vdm_diffuse_pack + vdm_loss_terms_rng; VDM4CDM_FUSED_HEAD=0: randn -> diffuse -> pack_input, A/B)
-FUSED_HEAD = os.environ.get("VDM4CDM_FUSED_HEAD", "1") != "0"
+# Fused head of the HIP training step (vdm_diffuse_pack + vdm_loss_terms_rng; fused_head=0: randn -> diffuse -> pack_input, A/B)
+FUSED_HEAD = bool(_experiment.get("fused_head"))
 
 
 class _DiffusionLossFn(torch.autograd.Function):
