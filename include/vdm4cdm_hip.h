@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VDM_ABI_VERSION 20
+#define VDM_ABI_VERSION 21
 
 typedef enum { VDM_OK = 0, VDM_ERR_ARG = -1, VDM_ERR_HIP = -2, VDM_ERR_UNSUPPORTED = -3 } vdm_status;
 typedef enum { VDM_F32 = 0, VDM_BF16 = 1 } vdm_dtype;
@@ -343,6 +343,27 @@ int vdm_diffuse_pack_fields(const float* x, const float* cond, int k, const floa
                             void* packed, void* stream);
 int vdm_conv_in_dgrad_fields(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
                              float* dz, float* ds, int n_ds, void* stream);
+
+/* ---- flow matching: fused head and loss of an SFM training step (ABI v21) [sfm_model.LightSFM of the trainSFM3D* scripts, REF
+ * trainSFM3D128_c_c_from_field_name_thick_lowbatch.py:112-127; the straight path between the paired fields x0 (source) and x1 (target)] --
+ * Fields are fp32, contiguous per sample of `per` elements; per % 4 == 0 and every non-NULL field pointer 16-byte aligned.  Every
+ * argument error (a required pointer NULL, n <= 0, per <= 0, per % 4 != 0, misalignment, bad dtype, sigma < 0 or NaN, cond outside
+ * {0, 1}, n > VDM_REDUCE_WS_ROWS for the loss) returns VDM_ERR_ARG with a message before any launch.
+ *   vdm_sfm_head: x_t = (1 - t[n]) x0 + t[n] x1, plus sigma eps when sigma > 0; written as fp32 (x_t, may be NULL) and, always, as
+ *     conv_in's NDHWC input packed[n][voxel][16 B] = {x_t, cond ? x0 : 0, 0 ...} in `dtype`, rounded like vdm_pack_input - one pass
+ *     instead of vdm_diffuse (+ vdm_randn + vdm_diffuse) + vdm_pack_input.  eps == NULL with sigma > 0: the noise is drawn inside the
+ *     kernel from the Philox counters (seed mixed with *seed_step, stream_id, float4 group index over the batch) - exactly the field
+ *     vdm_randn(seed, stream_id, seed_step) writes.  sigma == 0: neither eps nor the generator is touched (seed, stream_id and
+ *     *seed_step do not matter).  The bits are those of the chain: 1 - t rounded to fp32, then vdm_diffuse(x = x1, eps = x0, alpha = t,
+ *     sigma = 1 - t), then vdm_diffuse(x = x_t, eps, alpha = 1, sigma).
+ *   vdm_sfm_loss: sums[n] += sum (v_hat - (x1 - x0))^2 (caller zeroes sums, n floats) and d_v = coef[n] (v_hat - (x1 - x0)); the target
+ *     velocity field is never written.  Fixed-order two-stage reduction, no float atomics (bit-reproducible): sums and d_v carry the bits
+ *     of vdm_loss_terms_rng's first sum and d_eps_hat for eps = the materialised x1 - x0.  workspace as vdm_loss_terms
+ *     (VDM_REDUCE_WS_ROWS * 3 floats, n <= VDM_REDUCE_WS_ROWS). */
+int vdm_sfm_head(const float* x0, const float* x1, const float* eps, uint64_t seed, uint64_t stream_id, const int32_t* seed_step,
+                 const float* t, float sigma, int cond, int n, int64_t per, int dtype, float* x_t, void* packed, void* stream);
+int vdm_sfm_loss(const float* v_hat, const float* x0, const float* x1, const float* coef, int n, int64_t per, float* sums, float* d_v,
+                 float* workspace, void* stream);
 
 /* ---- data path: crop + log-normalise + flip + permute on the device -----------------------------
  * Replaces the per-sample CPU DataLoader work of [REF src/dataset/CAMELS_3D_dataset.py:53-73] (AstroDataset.__getitem__) and

@@ -81,7 +81,7 @@ PACK_CHUNK = 16384                   # VDM_PACK_CHUNK
 _p, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 _D = C.POINTER(ConvDesc)
 _T = C.POINTER(DdnmTables)
-ABI_VERSION = 20                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
+ABI_VERSION = 21                     # VDM_ABI_VERSION of include/vdm4cdm_hip.h this binding was written for
 
 # name -> (restype, argtypes); mirrors include/vdm4cdm_hip.h one to one
 SIGNATURES = {
@@ -135,6 +135,8 @@ SIGNATURES = {
     "vdm_pack_fields": (_i, [_p, _p, _i, _i, _i64, _i, _p, _p]),
     "vdm_diffuse_pack_fields": (_i, [_p, _p, _i, _p, _u64, _u64, _p, _p, _p, _i, _i64, _i, _p, _p, _p]),
     "vdm_conv_in_dgrad_fields": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
+    "vdm_sfm_head": (_i, [_p, _p, _p, _u64, _u64, _p, _p, _f, _i, _i, _i64, _i, _p, _p, _p]),
+    "vdm_sfm_loss": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _p]),
     "vdm_schedule_grad_sums": (_i, [_p, _p, _p, _u64, _u64, _p, _i, _i64, _p, _p, _p]),
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),

@@ -764,6 +764,87 @@ __global__ void __launch_bounds__(256) diffuse_pack_fields_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Flow matching (ABI v21): the head and the loss of an SFM training step.  Their arithmetic is pinned, bit for bit, to the chain of
+// generic launches they replace; the roundings are spelled out (fmaf / uncontracted_mul) as -ffp-contract=fast contracts the older
+// kernels' expressions, so that equality does not rest on two copies of one source line being contracted alike.
+//   sfm_interp : diffuse_kernel's al * x + si * e for (x = x1, e = x0, al = t, si = 1 - t) = fma(t, x1, (1 - t) * x0), then the same
+//                expression for (x = x_t, e = eps, al = 1, si = sigma) = x_t + sigma * eps (product rounded, then one add)
+//   sfm_sq4    : loss_terms_rng_kernel's (d0 d0 + d1 d1) + (d2 d2 + d3 d3) = fma(d0, d0, d1 * d1) + fma(d2, d2, d3 * d3)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float sfm_interp(float t, float omt, float x0, float x1, bool noisy, float sigma, float e) {
+    const float xt = fmaf(t, x1, uncontracted_mul(omt, x0));
+    return noisy ? xt + uncontracted_mul(sigma, e) : xt;
+}
+
+__device__ __forceinline__ float sfm_sq4(float d0, float d1, float d2, float d3) {
+    return fmaf(d0, d0, uncontracted_mul(d1, d1)) + fmaf(d2, d2, uncontracted_mul(d3, d3));
+}
+
+// Head: x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps), written once as fp32 (optional) and once as conv_in's packed input
+// {x_t, cond ? x0 : 0, 0 ...} - diffuse + (randn + diffuse) + pack_input in one pass.  Ownership and re-deal of diffuse_pack_kernel: a
+// thread owns 4 consecutive voxels (one Philox call, the counters of randn_kernel), deal_pieces stores 1 KiB per instruction.
+// sigma == 0 (uniform): neither eps nor the generator is touched.
+template <typename T>
+__global__ void __launch_bounds__(256) sfm_head_kernel(const float* __restrict__ x0, const float* __restrict__ x1, const float* __restrict__ eps,
+                                                      uint64_t seed0, uint64_t sid, const int32_t* __restrict__ seed_step,
+                                                      const float* __restrict__ t, float sigma, int cond, int64_t per,
+                                                      float* __restrict__ x_t, T* __restrict__ packed, int blocks_per_n) {
+    constexpr int EPL = DT<T>::EPL;
+    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
+    const bool noisy = sigma > 0.f;
+    const uint64_t seed = noisy && !eps ? mix_seed(seed0, seed_step) : 0;
+    const float tn = t[n], omt = 1.0f - tn;                        // (1 - t rounded to fp32 first, as the chain's host expression)
+    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
+    const size_t base = (size_t)n * per;
+    const float4* a4 = reinterpret_cast<const float4*>(x0 + base);
+    const float4* b4 = reinterpret_cast<const float4*>(x1 + base);
+    const float4* e4 = noisy && eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
+    float4* z4 = x_t ? reinterpret_cast<float4*>(x_t + base) : nullptr;
+    const int lane = threadIdx.x & 63;
+    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform: the shuffles need every lane
+    for (int64_t it = 0; it < rounds; ++it) {
+        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
+        const bool ok = i < n4;
+        const int64_t ic = ok ? i : n4 - 1;
+        const float4 av = a4[ic], bv = b4[ic];
+        float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (noisy) ev = e4 ? e4[ic] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + ic));
+        const float zz[4] = {sfm_interp(tn, omt, av.x, bv.x, noisy, sigma, ev.x), sfm_interp(tn, omt, av.y, bv.y, noisy, sigma, ev.y),
+                             sfm_interp(tn, omt, av.z, bv.z, noisy, sigma, ev.z), sfm_interp(tn, omt, av.w, bv.w, noisy, sigma, ev.w)};
+        float cc[1][4] = {{0.f, 0.f, 0.f, 0.f}};
+        if (cond) { cc[0][0] = av.x; cc[0][1] = av.y; cc[0][2] = av.z; cc[0][3] = av.w; }
+        if (z4 && ok) z4[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
+        deal_pieces<T, 1>(zz, cc, lane, i - lane, per, packed + base * EPL);
+    }
+}
+
+// Loss: part[block] = sum (v_hat - (x1 - x0))^2 and d_v = coef[n] (v_hat - (x1 - x0)); the target field is never written.  The residual,
+// the per-thread accumulation and the block fold are those of loss_terms_rng_kernel's first sum on the materialised target (x1 - x0 is
+// what diffuse_kernel gives for alpha = 1, sigma = -1: one rounded subtraction).
+__global__ void __launch_bounds__(256) sfm_loss_kernel(const float* __restrict__ vh, const float* __restrict__ x0, const float* __restrict__ x1,
+                                                      const float* __restrict__ coef, int64_t per, float* __restrict__ part,
+                                                      float* __restrict__ dv, int blocks_per_n) {
+    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
+    const float cf = coef[n];
+    const size_t base = (size_t)n * per;
+    const int64_t n4 = per >> 2;
+    const float4* h4 = reinterpret_cast<const float4*>(vh + base);
+    const float4* a4 = reinterpret_cast<const float4*>(x0 + base);
+    const float4* b4 = reinterpret_cast<const float4*>(x1 + base);
+    float4* d4 = reinterpret_cast<float4*>(dv + base);
+    float acc[1] = {0.f};
+    for (int64_t i = (int64_t)bn * 256 + threadIdx.x; i < n4; i += (int64_t)blocks_per_n * 256) {
+        const float4 hv = h4[i], av = a4[i], bv = b4[i];
+        const float d0 = hv.x - (bv.x - av.x), d1 = hv.y - (bv.y - av.y), d2 = hv.z - (bv.z - av.z), d3 = hv.w - (bv.w - av.w);
+        acc[0] += sfm_sq4(d0, d1, d2, d3);
+        d4[i] = make_float4(cf * d0, cf * d1, cf * d2, cf * d3);
+    }
+    __shared__ float sm[4];
+    block_sum<1>(acc, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc[0];
+}
+
 // K8 with the noise fields regenerated from their Philox counters instead of read (eps / eps0 NULL): the two 4-byte-per-element
 // fields of a training step never exist in memory.  Vector form of loss_terms_kernel (4 elements per thread; per % 4 == 0).
 __global__ void __launch_bounds__(256) loss_terms_rng_kernel(const float* __restrict__ x, const float* __restrict__ eps, uint64_t seed_e0,
@@ -1350,6 +1431,46 @@ extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t see
                        seed_eps0, stream_eps0, seed_step, s0a0, coef, per, workspace, d_eps_hat, bpn);
     hipLaunchKernelGGL(fold_partials_kernel, dim3(n * 3), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, bpn, 3, sums, 1);
     VDM_LAUNCH_CHECK("loss_terms_rng_kernel");
+    return VDM_OK;
+}
+
+extern "C" int vdm_sfm_head(const float* x0, const float* x1, const float* eps, uint64_t seed, uint64_t stream_id, const int32_t* seed_step,
+                            const float* t, float sigma, int cond, int n, int64_t per, int dtype, float* x_t, void* packed, void* stream) {
+    VDM_REQUIRE(x0 && x1 && t && packed, "sfm_head: NULL pointer (x0, x1, t and packed are required)");
+    VDM_REQUIRE(n > 0 && per > 0, "sfm_head: bad sizes n=%d per=%lld", n, (long long)per);
+    VDM_REQUIRE(per % 4 == 0, "sfm_head: per=%lld must be a multiple of 4", (long long)per);
+    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "sfm_head: bad dtype %d", dtype);
+    VDM_REQUIRE(sigma >= 0.f, "sfm_head: sigma=%g must be >= 0", (double)sigma);                     // (refuses NaN too)
+    VDM_REQUIRE(cond == 0 || cond == 1, "sfm_head: cond=%d must be 0 or 1", cond);
+    VDM_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)eps | (uintptr_t)x_t | (uintptr_t)packed) & 15) == 0 &&
+                    (((uintptr_t)t | (uintptr_t)seed_step) & 3) == 0,
+                "sfm_head: x0, x1, eps, x_t and packed must be 16-byte aligned, t / seed_step 4-byte aligned");
+    const int bpn = bpn_for(per / 4, n);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == VDM_F32)
+        hipLaunchKernelGGL(sfm_head_kernel<float>, dim3(bpn * n), dim3(256), 0, s, x0, x1, eps, seed, stream_id, seed_step, t, sigma, cond, per, x_t,
+                           (float*)packed, bpn);
+    else
+        hipLaunchKernelGGL(sfm_head_kernel<bf16_t>, dim3(bpn * n), dim3(256), 0, s, x0, x1, eps, seed, stream_id, seed_step, t, sigma, cond, per,
+                           x_t, (bf16_t*)packed, bpn);
+    VDM_LAUNCH_CHECK("sfm_head_kernel");
+    return VDM_OK;
+}
+
+extern "C" int vdm_sfm_loss(const float* v_hat, const float* x0, const float* x1, const float* coef, int n, int64_t per, float* sums,
+                            float* d_v, float* workspace, void* stream) {
+    VDM_REQUIRE(v_hat && x0 && x1 && coef && sums && d_v && workspace, "sfm_loss: NULL pointer (every argument but stream is required)");
+    VDM_REQUIRE(n > 0 && per > 0, "sfm_loss: bad sizes n=%d per=%lld", n, (long long)per);
+    VDM_REQUIRE(per % 4 == 0, "sfm_loss: per=%lld must be a multiple of 4", (long long)per);
+    VDM_REQUIRE(n <= VDM_REDUCE_WS_ROWS, "sfm_loss: at most %d samples per call (got %d): the workspace holds one partial row per block",
+                VDM_REDUCE_WS_ROWS, n);
+    VDM_REQUIRE((((uintptr_t)v_hat | (uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)d_v) & 15) == 0 &&
+                    (((uintptr_t)coef | (uintptr_t)sums | (uintptr_t)workspace) & 3) == 0,
+                "sfm_loss: v_hat, x0, x1 and d_v must be 16-byte aligned, coef / sums / workspace 4-byte aligned");
+    const int bpn = bpn_for(per / 4, n);
+    hipLaunchKernelGGL(sfm_loss_kernel, dim3(bpn * n), dim3(256), 0, (hipStream_t)stream, v_hat, x0, x1, coef, per, workspace, d_v, bpn);
+    hipLaunchKernelGGL(fold_partials_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, bpn, 1, sums, 1);
+    VDM_LAUNCH_CHECK("sfm_loss_kernel");
     return VDM_OK;
 }
 

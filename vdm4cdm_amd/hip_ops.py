@@ -854,6 +854,47 @@ def loss_terms(x, eps, eps_hat, eps0, sigma0_over_alpha0, coef, sums, d_eps_hat,
                            _p(sums), _p(d_eps_hat), _p(ws), _s()), "vdm_loss_terms")
 
 
+def sfm_head(x0, x1, t, sigma, dtype, cond=True, eps=None, seed=0, stream_id=0, want_x=False, x_out=None, packed_out=None):
+    """Fused head of the flow-matching step (vdm_sfm_head): x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps when sigma > 0) -> (x_t fp32 or
+    None, conv_in's NDHWC input [N, D, H, W, cpad(2)] = {x_t, x0 if cond else 0, 0...} in `dtype`).  eps None with sigma > 0: drawn inside
+    the kernel from Philox(seed, stream_id) - the field randn(out, seed, stream_id) would have written; sigma == 0: no noise is read or
+    drawn.  x_out / packed_out: write there instead of into fresh tensors (x_out implies want_x).  The kernel owns 4 voxels per thread:
+    a sample whose voxel count is no multiple of 4 is refused (ValueError)."""
+    n = x0.shape[0]
+    per = x0.numel() // n
+    if per % 4:
+        raise ValueError(f"sfm_head: {per} voxels per sample is not a multiple of 4")
+    L = _lib.lib()
+    _contig(x0, x1, t, eps, x_out, packed_out)
+    assert x0.dtype == x1.dtype == t.dtype == torch.float32 and x1.shape == x0.shape and t.numel() == n
+    assert eps is None or (eps.dtype == torch.float32 and eps.shape == x0.shape)
+    sp = tuple(x0.shape[2:]) if x0.dim() == 5 else tuple(x0.shape[1:])
+    packed = packed_out if packed_out is not None else torch.empty((n,) + sp + (cpad(2, dtype),), dtype=dtype, device=x0.device)
+    assert packed.dtype == dtype and packed.numel() == x0.numel() * cpad(2, dtype)
+    x_t = x_out if x_out is not None else (torch.empty_like(x0) if want_x else None)
+    assert x_t is None or (x_t.dtype == torch.float32 and x_t.numel() == x0.numel())
+    check(L.vdm_sfm_head(_p(x0), _p(x1), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(t), float(sigma), int(bool(cond)), n, per,
+                         dt_id(dtype), _p(x_t), _p(packed), _s()), "vdm_sfm_head")
+    return x_t, packed
+
+
+def sfm_loss(v_hat, x0, x1, coef, sums, d_v, workspace=None):
+    """Flow-matching loss (vdm_sfm_loss): sums[n] += sum (v_hat - (x1 - x0))^2, d_v = coef[n] (v_hat - (x1 - x0)); the target field is never
+    written.  sums: [N] fp32, zeroed by the caller.  workspace: the caller's 2048 * 3 floats instead of the cached scratch.  A sample whose
+    element count is no multiple of 4 is refused (ValueError).  (No generator is involved: SEED_STEP has nothing to reach here.)"""
+    n = x0.shape[0]
+    per = x0.numel() // n
+    if per % 4:
+        raise ValueError(f"sfm_loss: {per} elements per sample is not a multiple of 4")
+    L = _lib.lib()
+    ws = workspace if workspace is not None else _reduce_ws(x0.device)
+    assert ws.dtype == torch.float32 and ws.numel() >= 2048 * 3
+    _contig(v_hat, x0, x1, coef, sums, d_v)
+    assert v_hat.dtype == x0.dtype == x1.dtype == coef.dtype == sums.dtype == d_v.dtype == torch.float32
+    assert v_hat.numel() == x0.numel() == x1.numel() == d_v.numel() and coef.numel() == n and sums.numel() == n
+    check(L.vdm_sfm_loss(_p(v_hat), _p(x0), _p(x1), _p(coef), n, per, _p(sums), _p(d_v), _p(ws), _s()), "vdm_sfm_loss")
+
+
 def ancestral_step(z, eps_hat, noise, coef, step_ptr, seed, eps_uncond=None, w_cfg=0.0):
     """K9.  eps_uncond given: classifier-free guidance, (1 + w_cfg) * eps_hat - w_cfg * eps_uncond blended inside the update."""
     L = _lib.lib()

@@ -14,15 +14,42 @@ Lipman et al. 2023 / Tong et al. 2023 (I-CFM) on the straight path between the p
     loss = mean over batch and elements of (v_theta(x_t, t; s_conditioning = x0, v_conditionings) - u)^2
     sample: x <- x + v_theta(x, t_i; x0, v) / n,  t_i = i / n, starting from x = x0       (explicit Euler, n steps)
 
-On the HIP backend the interpolation / target are the K7 kernel (``vdm_diffuse``: a x + b y per sample), the loss and its
-gradient the K8 kernel, and the Euler loop is the same captured hipGraph as the VDM sampler (``sampling.hip_graph_sampler``) with
-the coefficient table {1, -1/n, 0, t_i}.
+On the HIP backend the training step is two kernels around the network: ``vdm_sfm_head`` forms x_t straight into conv_in's packed input
+(noise drawn in the kernel) and ``vdm_sfm_loss`` reduces the residual and writes its gradient - x_t, eps and u never exist in memory, and
+the step can be captured in a hipGraph (``trainer.GraphedTrainStep``; the times then come from the device step counter).  With
+``VDM4CDM_EXPERIMENT=fused_head=0``, or a cube whose voxel count is no multiple of 4, the interpolation / target are the K7 kernel
+(``vdm_diffuse``: a x + b y per sample) and the loss and its gradient the K8 kernel: the same bits, launch by launch.  The Euler loop is
+the same captured hipGraph as the VDM sampler (``sampling.hip_graph_sampler``) with the coefficient table {1, -1/n, 0, t_i}.
 """
 import torch
 import torch.nn as nn
 
+from . import _experiment
 from .sampling import ChainNoise, hip_graph_sampler
 from .vdm_model import _DiffusionLossFn, stratified_times
+
+# Fused head and loss of the HIP training step (vdm_sfm_head + vdm_sfm_loss; fused_head=0: diffuse -> (randn -> diffuse) -> diffuse ->
+# pack_input -> the VDM loss kernel, A/B) - the VDM's switch, no new one
+FUSED_HEAD = bool(_experiment.get("fused_head"))
+
+
+class _SfmLossFn(torch.autograd.Function):
+    """0.5 sum_n coef_n sum (v_hat - (x1 - x0))^2 through vdm_sfm_loss; d loss / d v_hat = coef_n (v_hat - (x1 - x0)) comes out of the
+    same pass.  No gradient reaches x0 / x1."""
+
+    @staticmethod
+    def forward(ctx, v_hat, x0, x1, coef):
+        from . import hip_ops as ops
+        d = torch.empty_like(v_hat)
+        sums = torch.zeros(x1.shape[0], device=x1.device)
+        ops.sfm_loss(v_hat.contiguous(), x0, x1, coef, sums, d)
+        ctx.save_for_backward(d)
+        return 0.5 * (coef * sums).sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return g * d, None, None, None
 
 
 class SFM(nn.Module):
@@ -46,12 +73,56 @@ class SFM(nn.Module):
             kw["s_conditioning"] = x0
         return net(xt, t=t, v_conditionings=list(v_conditionings or []), **kw)
 
+    def graph_capturable(self):
+        """(can trainer.GraphedTrainStep capture this model's step?, the reason if not).  The captured step takes its times from
+        vdm_train_scalars (the stratified grid, u0 from the device step counter); independent uniform times are drawn on the host."""
+        if not self.antithetic_time_sampling:
+            return False, "antithetic_time_sampling=False draws the times from a host generator"
+        return True, ""
+
+    def _fused_loss(self, ops, x0, x1, t, eps, v_conditionings):
+        """The HIP step without the chain: vdm_sfm_head forms x_t straight into conv_in's packed input (x_t itself, the noise field and
+        the target x1 - x0 never exist in memory), vdm_sfm_loss reduces the residual and writes d loss / d v.  Same bits as the chain."""
+        from .vdm_model import VDM, noise_seed
+        net = self.velocity_model
+        B, numel = x1.shape[0], x1[0].numel()
+        cond = 1 if getattr(net, "s_conditioning_channels", 1) else 0
+        seed, sid, e = 0, 0, None
+        if self.sigma > 0.0:
+            if eps is None:
+                seed, sid = noise_seed(), 2 * VDM._rank_world()[0] + 1                   # (drawn where the chain's ops.randn draws it)
+            else:
+                e = eps.to(device=x1.device, dtype=torch.float32).contiguous()
+        dt = torch.bfloat16 if net.precision == "bf16" else torch.float32
+        _, xin = ops.sfm_head(x0, x1, t.contiguous(), self.sigma, dt, cond=cond, eps=e, seed=seed, stream_id=sid)
+        kw = {"s_conditioning": x0} if cond else {}
+        # (x1 stands in for x_t: with a packed input the network reads only the shape of its first argument)
+        v = net(x1, t=t, v_conditionings=list(v_conditionings or []), _packed_input=xin, **kw)
+        coef = torch.full((B,), 2.0 / (B * numel), device=x1.device)                     # loss = 0.5 sum_n coef_n S_n = mean sq. error
+        return _SfmLossFn.apply(v, x0, x1, coef)
+
     def get_loss(self, x0, x1, times=None, eps=None, v_conditionings=None):
         B, numel = x1.shape[0], x1[0].numel()
         x0, x1 = x0.to(torch.float32).contiguous(), x1.to(torch.float32).contiguous()
-        t = stratified_times(B, x1.device, self.antithetic_time_sampling) if times is None else times.to(x1.device, torch.float32)
-        if self._hip(x1):
+        hip = self._hip(x1)
+        if hip:
             from . import hip_ops as ops
+        if times is not None:
+            t = times.to(x1.device, torch.float32)
+        elif hip and self.antithetic_time_sampling and ops.SEED_STEP is not None:
+            # graph-captured step (trainer.GraphedTrainStep): the VDM's stratified grid over the global batch, u0 drawn in the kernel from
+            # one fixed seed and the device step counter (row 0 of vdm_train_scalars; the schedule rows are not used)
+            from .vdm_model import VDM, noise_seed
+            if getattr(self, "_graph_seed", None) is None:
+                self._graph_seed = noise_seed()
+            rank, world = VDM._rank_world()
+            t = ops.train_scalars(B, x1.device, rank, world, 0.0, 1.0, 1.0, seed=self._graph_seed)[0]
+        else:
+            t = stratified_times(B, x1.device, self.antithetic_time_sampling)
+        if hip and FUSED_HEAD and numel % 4 == 0 and x1.dim() == 5 and x0.shape == x1.shape \
+                and getattr(self.velocity_model, "s_conditioning_channels", 1) <= 1:
+            loss = self._fused_loss(ops, x0, x1, t, eps, v_conditionings)
+        elif hip:
             one = torch.ones(B, device=x1.device)
             xt = ops.diffuse(x1, x0, t.contiguous(), (1.0 - t).contiguous())            # t x1 + (1 - t) x0
             if self.sigma > 0.0:
@@ -146,12 +217,18 @@ class LightSFM(nn.Module):
         self.log_dict({f"val/{k}": v for k, v in metrics.items()})
         return loss
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, capturable=False):
+        """capturable: the optimizer state (step count) lives on the device, so that the step can be captured in a hipGraph
+        (trainer.GraphedTrainStep)."""
         fused = all(p.is_cuda for p in self.parameters())
-        opt = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, fused=fused)
+        opt = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, fused=fused, capturable=bool(capturable and fused))
         vm = self.model.velocity_model
-        if hasattr(vm, "mark_weights_dirty"):
-            opt.register_step_post_hook(lambda *_: vm.mark_weights_dirty())
+        if hasattr(vm, "mark_weights_dirty"):      # fused steps do not bump Tensor._version: tell the HIP executor to re-pack
+            def _after_step(*_):
+                vm.mark_weights_dirty()
+                if hasattr(vm, "repack_weights"):
+                    vm.repack_weights()
+            opt.register_step_post_hook(_after_step)
         return opt
 
     def draw_samples(self, x0=None, n_sampling_steps=100, batch_size=None, verbose=False, return_all=False, **kwargs):

@@ -125,6 +125,18 @@ def set_rng_state(model, device, st):
         model.load_rng_state_dict(st.get("model") or {})
 
 
+def batch_shapes(batch):
+    """The shapes of every tensor of a batch dict (lists of tensors entry by entry, anything else as None): what a captured step is
+    static in, whatever the batch's keys are ({"x", "conditioning", ...} of the VDM, {"x0", "x1", ...} of flow matching)."""
+    def one(v):
+        if torch.is_tensor(v):
+            return tuple(v.shape)
+        if isinstance(v, (list, tuple)):
+            return tuple(one(a) for a in v)
+        return None
+    return {k: one(v) for k, v in batch.items()}
+
+
 def read_checkpoint(path, mmap=False):
     """A checkpoint file on the host (tensors on the CPU; mmap: mapped, so that reading `global_step` does not read the weights)."""
     return torch.load(path, map_location="cpu", mmap=bool(mmap), weights_only=True)
@@ -157,6 +169,7 @@ class GraphedTrainStep:
             set_rng_state(model, dev, state["rng"])
         self.rng_before = rng_state(model, dev)
         self.static = {k: ([t.clone() for t in v] if isinstance(v, (list, tuple)) else (None if v is None else v.clone())) for k, v in batch.items()}
+        self.shapes = batch_shapes(batch)                       # a batch of other shapes (a ragged last one) is not for this graph
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         # The device counter is mixed into the seeds ONLY while this object's own step runs (hip_ops.SEED_STEP is set inside _step and
         # cleared on the way out): eager steps of the same process - a ragged last batch, validation, a later fit - keep drawing u0 and
@@ -349,7 +362,13 @@ class Trainer:
         if hasattr(sm, "enable_ddp") and dev_type == "cuda":     # HIP backend: bucketed all-reduce inside the backward pass
             sm.enable_ddp(self.world)
         use_hip = dev_type == "cuda" and getattr(model.model.score_model, "backend", "") == "hip"
-        graphed = self.graph_step and use_hip and self.world == 1 and getattr(model.model, "noise_schedule", "") == "fixed_linear"
+        graphed = self.graph_step and use_hip and self.world == 1
+        if graphed and hasattr(model.model, "graph_capturable"):      # (flow matching: the model says whether its step can be captured)
+            graphed, why = model.model.graph_capturable()
+            if not graphed and self.rank == 0:
+                print(f"Trainer: {why} - the training step stays eager", flush=True)
+        elif graphed:
+            graphed = getattr(model.model, "noise_schedule", "") == "fixed_linear"
         if use_hip:
             from . import _experiment
             _experiment.refuse_for_training()      # timing switches of tools/ablate_step.sh skip kernels: never train with them
@@ -391,7 +410,7 @@ class Trainer:
                     if graphed and gstep is None and (graph_state is not None or self.max_steps - self.global_step >= 8):
                         # captured at the first batch (its eager warm-up steps are undone: parameters / optimizer state restored)
                         gstep = ctx["gstep"] = GraphedTrainStep(model, opt, params, self.gradient_clip_val, batch, state=graph_state)
-                    if gstep is not None and gstep.static["x"].shape == batch["x"].shape:
+                    if gstep is not None and gstep.shapes == batch_shapes(batch):
                         loss, gnorm = gstep(batch), gstep.gnorm   # one hipGraph replay = the whole step
                     else:                                         # eager step (N > 1 ranks, short runs, a ragged last batch, the torch backend)
                         loss = model.training_step(batch, self.global_step)
