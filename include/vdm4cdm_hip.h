@@ -469,6 +469,20 @@ int vdm_ancestral_step_cfg(float* z, const float* eps_cond, const float* eps_unc
  * DEVICE array of `rows` values; per_row must be a positive multiple of 4 and the three fields 16-byte aligned. */
 int vdm_ancestral_step_rows(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, const float* coef,
                             const int32_t* step_ptr, const uint64_t* seeds, int rows, int64_t per_row, void* stream);
+/* ---- K9m: multistep update (DPM-Solver++(2M) on the VDM's data prediction; Adams-Bashforth 2 on the flow-matching velocity) ----
+ * Per element, with the scalars of row *step_ptr of the DEVICE table coef[steps][8] = {e_z, e_e, w_z, w_x, w_p, t_net, 0, 0} (so one
+ * captured graph serves every step) and rn() one fp32 rounding:
+ *   e    = eps_uncond ? rn(rn(rn(1 + w_cfg) * eps_hat) - rn(w_cfg * eps_uncond)) : eps_hat      (the blend of vdm_ancestral_step_cfg)
+ *   est  = fma(e_z, z, rn(e_e * e))             data prediction (VDM: e_z = 1/alpha_t, e_e = -sigma_t/alpha_t) or velocity (0, 1)
+ *   a    = fma(w_z, z, rn(w_x * est))
+ *   z    <- w_p != 0 ? fma(w_p, prev, a) : a
+ *   prev <- est
+ * The sequence is spelled out in the kernel (fmaf and separately rounded products), so both libraries give the same bits whatever the
+ * compiler contracts.  A row with w_p == 0 (a first-order step; always the first one) does NOT read prev: the history does not exist
+ * yet and the buffer may hold anything, NaN included; prev is still written.  Any n >= 1; 16-byte aligned fields go through float4
+ * loads and stores with a ragged tail.  z, eps_hat, prev, coef or step_ptr NULL, or n <= 0: VDM_ERR_ARG, nothing is launched. */
+int vdm_multistep_step(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, float* prev, const float* coef,
+                       const int32_t* step_ptr, int64_t n, void* stream);
 /* standard-normal fill from Philox(seed, stream_id) (z_1 of the sampler; eps in training). */
 int vdm_randn(float* out, int64_t n, uint64_t seed, uint64_t stream_id, const int32_t* seed_step, void* stream);
 /* *step_ptr += 1 (device-side step counter for the captured sampler graph). */

@@ -141,6 +141,7 @@ SIGNATURES = {
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_rows": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i64, _p]),
+    "vdm_multistep_step": (_i, [_p, _p, _p, _f, _p, _p, _p, _i64, _p]),
     "vdm_ddnm_x0": (_i, [_p, _p, _p, _f, _T, _p, _i64, _p]),
     "vdm_ddnm_update": (_i, [_p, _p, _p, _p, _i, _p, _T, _p, _i, _i64, _p]),
     "vdm_ddnm_mask_step": (_i, [_p, _p, _p, _f, _p, _i, _p, _i, _p, _T, _p, _i, _i64, _p]),

@@ -974,6 +974,63 @@ __global__ void __launch_bounds__(256) ancestral_rows_kernel(float* __restrict__
     }
 }
 
+// K9m: one element of the multistep update (DPM-Solver++(2M) on the VDM's data prediction, Adams-Bashforth 2 on the flow-matching
+// velocity; a first-order row is DDIM / Euler).  Every rounding is spelled out, so both libraries give the same bits whatever the
+// compiler contracts:
+//   e   = cfg ? rn(rn(rn(1 + w) * eh) - rn(w * eu)) : eh            (the blend of ancestral_update)
+//   est = fma(e_z, z, rn(e_e * e))
+//   a   = fma(w_z, z, rn(w_x * est))
+//   z'  = hist ? fma(w_p, prev, a) : a
+// hist = (w_p != 0), the same for every lane: a row without history (the first step: the buffer is uninitialised and may hold NaN)
+// does not load prev at all.
+__device__ __forceinline__ float multistep_est(float z, float eh, float eu, bool cfg, float w, float e_z, float e_e) {
+    const float e = cfg ? uncontracted_mul(1.f + w, eh) - uncontracted_mul(w, eu) : eh;
+    return fmaf(e_z, z, uncontracted_mul(e_e, e));
+}
+
+__device__ __forceinline__ float multistep_update(float z, float est, float prev, bool hist, float w_z, float w_x, float w_p) {
+    const float a = fmaf(w_z, z, uncontracted_mul(w_x, est));
+    return hist ? fmaf(w_p, prev, a) : a;
+}
+
+// z <- w_z z + w_x est + w_p prev, prev <- est at the row *step_ptr of coef[steps][8] = {e_z, e_e, w_z, w_x, w_p, t_net, 0, 0}.  The
+// first n_vec float4 groups go through 16-byte loads and stores (n_vec = 0 when a field is not 16-byte aligned), the ragged tail
+// [4 n_vec, n) element by element.
+__global__ void __launch_bounds__(256) multistep_kernel(float* __restrict__ z, const float* __restrict__ eh,
+                                                       const float* __restrict__ eu, float w, float* __restrict__ prev,
+                                                       const float* __restrict__ coef, const int32_t* __restrict__ step_ptr,
+                                                       int64_t n_vec, int64_t n) {
+    const float* row = coef + (size_t)(*step_ptr) * 8;
+    const float e_z = row[0], e_e = row[1], w_z = row[2], w_x = row[3], w_p = row[4];
+    const bool hist = w_p != 0.f, cfg = eu != nullptr;
+    float4* z4 = reinterpret_cast<float4*>(z);
+    float4* p4 = reinterpret_cast<float4*>(prev);
+    const float4* h4 = reinterpret_cast<const float4*>(eh);
+    const float4* u4 = reinterpret_cast<const float4*>(eu);
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = tid; i < n_vec; i += stride) {
+        const float4 hv = h4[i];
+        const float4 uv = cfg ? u4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 pv = hist ? p4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 zv = z4[i], ev;
+        ev.x = multistep_est(zv.x, hv.x, uv.x, cfg, w, e_z, e_e);
+        ev.y = multistep_est(zv.y, hv.y, uv.y, cfg, w, e_z, e_e);
+        ev.z = multistep_est(zv.z, hv.z, uv.z, cfg, w, e_z, e_e);
+        ev.w = multistep_est(zv.w, hv.w, uv.w, cfg, w, e_z, e_e);
+        zv.x = multistep_update(zv.x, ev.x, pv.x, hist, w_z, w_x, w_p);
+        zv.y = multistep_update(zv.y, ev.y, pv.y, hist, w_z, w_x, w_p);
+        zv.z = multistep_update(zv.z, ev.z, pv.z, hist, w_z, w_x, w_p);
+        zv.w = multistep_update(zv.w, ev.w, pv.w, hist, w_z, w_x, w_p);
+        z4[i] = zv;
+        p4[i] = ev;
+    }
+    for (int64_t k = n_vec * 4 + tid; k < n; k += stride) {
+        const float est = multistep_est(z[k], eh[k], cfg ? eu[k] : 0.f, cfg, w, e_z, e_e);
+        z[k] = multistep_update(z[k], est, hist ? prev[k] : 0.f, hist, w_z, w_x, w_p);
+        prev[k] = est;
+    }
+}
+
 // out[c] = sum over rows of x[row][c] (bias gradients of the attention block's 1x1 projections); one workgroup per 16-byte piece
 // column, fixed summation order
 template <typename T>
@@ -1521,6 +1578,17 @@ extern "C" int vdm_ancestral_step_rows(float* z, const float* eps_hat, const flo
     hipLaunchKernelGGL(ancestral_rows_kernel, dim3((unsigned)bx, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, z, eps_hat, eps_uncond,
                        w_cfg, coef, step_ptr, seeds, per_row);
     VDM_LAUNCH_CHECK("ancestral_rows_kernel");
+    return VDM_OK;
+}
+
+extern "C" int vdm_multistep_step(float* z, const float* eps_hat, const float* eps_uncond, float w_cfg, float* prev, const float* coef,
+                                  const int32_t* step_ptr, int64_t n, void* stream) {
+    VDM_REQUIRE(z && eps_hat && prev && coef && step_ptr, "multistep_step: null z / eps_hat / prev / coef / step_ptr");
+    VDM_REQUIRE(n > 0, "multistep_step: n = %lld (must be positive)", (long long)n);
+    const bool aligned = (((uintptr_t)z | (uintptr_t)eps_hat | (uintptr_t)eps_uncond | (uintptr_t)prev) & 15) == 0;
+    hipLaunchKernelGGL(multistep_kernel, dim3(grid_for(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, z, eps_hat, eps_uncond, w_cfg, prev,
+                       coef, step_ptr, aligned ? n >> 2 : (int64_t)0, n);
+    VDM_LAUNCH_CHECK("multistep_kernel");
     return VDM_OK;
 }
 

@@ -12,7 +12,7 @@
 * ``generate_3D.py <model_name> <save_path> <runtype>`` -> ``generate_3d(argv)`` (/root/reference/generate_3D.py).
 Environment knobs (build-side, all optional): VDM4CDM_MAX_STEPS, VDM4CDM_PRECISION (bf16|fp32), VDM4CDM_SAMPLING_STEPS,
 VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing config), VDM4CDM_SAMPLE_BATCH (chains per sampler
-call and rank in generate_3D*; default 1), VDM4CDM_RESUME (a checkpoint of the same run to continue from, or "last": the newest one
+call and rank in generate_3D*; default 1), VDM4CDM_SAMPLER (ancestral | ddim | dpm2m: the sampler of generate_3D*), VDM4CDM_RESUME (a checkpoint of the same run to continue from, or "last": the newest one
 in the run directory).
 Multi-GPU: launch the same script under ``python -m torch.distributed.run --nproc-per-node N`` (one rank per GPU, RCCL).
 """
@@ -359,10 +359,19 @@ def _sample_batch():
     return int(raw)
 
 
-def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, world, n_steps, per_call=1):
+def _sampler_name():
+    """VDM4CDM_SAMPLER: ancestral (default) | ddim | dpm2m - the sampler of the generate scripts (VDM.sample(sampler=)).  Read before
+    any model or GPU work, so that a bad value fails at once."""
+    raw = os.environ.get("VDM4CDM_SAMPLER", "ancestral")
+    if raw not in ("ancestral", "ddim", "dpm2m"):
+        raise SystemExit(f"VDM4CDM_SAMPLER={raw!r}: must be one of ancestral, ddim, dpm2m")
+    return raw
+
+
+def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, world, n_steps, per_call=1, sampler="ancestral"):
     """The `rep` independent chains of one conditioning cube that fall to this rank: [(repetition index, sample)].  The rank's chains
     are sampled `per_call` at a time; every chain is keyed by its own seed (VDM.sample(seeds=)), so its cube does not depend on the
-    batch it was sampled in."""
+    batch it was sampled in.  sampler: VDM.sample(sampler=)."""
     s_conditioning = batch["conditioning"].to(device)
     v_conditionings = [d.to(device) for d in batch["conditioning_values"]] if config.get("conditioning_values", 6) else []
     mine = [i for i in range(rep) if (first_chain + i) % world == rank]    # global chain id first_chain + i: dealt round-robin to ranks
@@ -371,10 +380,10 @@ def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, wo
         ids = mine[k:k + per_call]
         if per_call == 1:
             gen = model.draw_samples(batch_size=1, n_sampling_steps=n_steps, seed=chain_seed(first_chain + ids[0]),
-                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0))
+                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0), sampler=sampler)
         else:
             gen = model.draw_samples(batch_size=len(ids), n_sampling_steps=n_steps, seeds=[chain_seed(first_chain + i) for i in ids],
-                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0))
+                                     s_conditioning=s_conditioning, v_conditionings=v_conditionings, verbose=(rank == 0), sampler=sampler)
         gen = gen.detach().cpu().numpy()
         out.extend((i, gen[j:j + 1]) for j, i in enumerate(ids))
     return out
@@ -422,6 +431,7 @@ def generate_3d(argv=None, configs_path=None):
         raise NotImplementedError("This model is not implemented yet")
     assert args.runtype in ["CV_12_12", "CV_1_128"]
     per_call = _sample_batch()
+    sampler = _sampler_name()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "CV")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -431,7 +441,7 @@ def generate_3d(argv=None, configs_path=None):
     for i_batch, batch in enumerate(dm.test_dataloader()):
         if sel is not None and i_batch != sel:
             continue
-        parts = _sample_repetitions(model, config, batch, device, rep, count * rep, rank, world, n_steps, per_call)
+        parts = _sample_repetitions(model, config, batch, device, rep, count * rep, rank, world, n_steps, per_call, sampler)
         _save_or_shard(args.save_path, f"gen_{count}", parts, rank, world)
         count += 1
         if count == n_cubes:
@@ -458,6 +468,7 @@ def generate_3d_1p(argv=None, configs_path=None):
     if args.runtype not in ["1P_24", "1P_128"]:
         raise NotImplementedError("This runtype is not implemented yet")
     per_call = _sample_batch()
+    sampler = _sampler_name()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "1P")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -469,7 +480,7 @@ def generate_3d_1p(argv=None, configs_path=None):
         k = ONE_P_GENS.index(i_batch)
         if rank == 0:
             print(ONE_P_NAMES[k], "params", batch["conditioning_values"], flush=True)
-        parts = _sample_repetitions(model, config, batch, device, rep, k * rep, rank, world, n_steps, per_call)
+        parts = _sample_repetitions(model, config, batch, device, rep, k * rep, rank, world, n_steps, per_call, sampler)
         stems.append(f"{ONE_P_NAMES[k]}_{rep}")
         _save_or_shard(args.save_path, stems[-1], parts, rank, world)
     _merge_shards(args.save_path, stems, rep, rank, world)

@@ -921,6 +921,18 @@ def ancestral_step_rows(z, eps_hat, coef, step_ptr, seeds_dev, eps_uncond=None, 
                                     z.numel() // rows, _s()), "vdm_ancestral_step_rows")
 
 
+def multistep_step(z, eps_hat, prev, coef, step_ptr, eps_uncond=None, w_cfg=0.0):
+    """K9m: est = e_z z + e_e e, z <- w_z z + w_x est + w_p prev, prev <- est, the scalars from row *step_ptr of coef [steps, 8] fp32 =
+    {e_z, e_e, w_z, w_x, w_p, t_net, 0, 0}; a row with w_p == 0 does not read prev.  eps_uncond: the w_cfg blend of K9."""
+    L = _lib.lib()
+    _contig(z, eps_hat, prev, coef, eps_uncond)
+    assert eps_hat.shape == prev.shape == z.shape and z.dtype == eps_hat.dtype == prev.dtype == coef.dtype == torch.float32
+    assert eps_uncond is None or (eps_uncond.shape == z.shape and eps_uncond.dtype == torch.float32)
+    assert coef.dim() == 2 and coef.shape[1] == 8 and step_ptr.dtype == torch.int32
+    check(L.vdm_multistep_step(_p(z), _p(eps_hat), _p(eps_uncond), float(w_cfg), _p(prev), _p(coef), _p(step_ptr), z.numel(), _s()),
+          "vdm_multistep_step")
+
+
 class DdnmTables:
     """The device tables behind the DDNM kernels (vdm_ddnm_tables): coef [n, 8] fp32 = {1/alpha_t, sigma_t, w_z, w_x, scale, t_norm, 0, 0},
     sched [n_sched, 2] int32 = {grid index k, draw number} per network evaluation, cursor int32 [1] (the evaluation index), k_ptr int32

@@ -1,6 +1,7 @@
 """Running a sampling chain: who draws which noise field from which key (``ChainNoise``), the network part of a step (``NetStep``), the
-capture-and-replay loop (``StepLoop``), and the samplers built from them - the ancestral / Euler device loop ``hip_graph_sampler`` and
-the DDNM sampler (``ddnm_sample``, ``hip_ddnm_sampler``).  The model itself (schedule, loss, one-step formulas, coefficient tables) is
+capture-and-replay loop (``StepLoop``), and the samplers built from them - the ancestral / Euler device loop ``hip_graph_sampler``, the
+deterministic multistep loop ``hip_multistep_sampler`` (DDIM, DPM-Solver++(2M), Adams-Bashforth 2; ``multistep_loop`` on the torch backend)
+and the DDNM sampler (``ddnm_sample``, ``hip_ddnm_sampler``).  The model itself (schedule, loss, one-step formulas, coefficient tables) is
 vdm_model.VDM; the torch-backend ancestral loop stays in ``VDM.sample``.
 The table of the keying rules (mode x {z_1, host draw d, device stream}) is in DESIGN.md section 4a-s.
 """
@@ -215,6 +216,62 @@ def hip_graph_sampler(net, z, coef, noise, verbose, use_graph, s_cond, v_conditi
         ops.step_inc(step)
     loop = StepLoop(one_step, z, step.zero_, noise, [[i] for i in range(coef.shape[0])], z, use_graph, return_all)
     return loop.run("sampling:", 50, verbose)
+
+
+# ------------------------------------------------------------------------------------------------------------- multistep
+VDM_SAMPLERS = ("ancestral", "ddim", "dpm2m")               # VDM.sample(sampler=); "ddim" is the order-1 multistep table
+
+
+def check_sampler(name, who="sample"):
+    if name not in VDM_SAMPLERS:
+        raise ValueError(f"{who}: sampler={name!r} (one of {', '.join(VDM_SAMPLERS)})")
+    return name
+
+
+class _NoStepNoise:
+    """What StepLoop asks of its noise source, for a deterministic sampler: no feed to prime, nothing to load per draw."""
+    feed = None
+
+    def load(self, d):
+        pass
+
+
+def hip_multistep_sampler(net, z, coef, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None, return_all=False):
+    """The deterministic multistep loop on the HIP backend (VDM: DDIM / DPM-Solver++(2M) on the data prediction, SFM: Euler /
+    Adams-Bashforth 2 on the velocity): per step [NetStep, K9m: est = e_z z + e_e net_out (the w_cfg blend inside it), z <- w_z z +
+    w_x est + w_p prev, prev <- est, step counter + 1]; coef[n][8] = {e_z, e_e, w_z, w_x, w_p, network time, 0, 0} is read on the device
+    at the row of the device-side step counter.  One field of history (`prev`), no step noise.  z is updated in place and returned;
+    return_all: the stack [n, B, ...] of z after every step instead."""
+    from . import hip_ops as ops
+    step = torch.zeros(1, dtype=torch.int32, device=z.device)
+    # prev is never initialised: row 0 has w_p = 0 and K9m does not read prev there.  StepLoop's warm-up replay runs step 0 and leaves
+    # its estimate in prev - harmless for the same reason (only z and the counter are put back).
+    prev = torch.empty_like(z)
+    net_step = NetStep(net, coef[:, 5].contiguous(), z, s_cond, v_conditionings, w_cfg, mask_fn)
+
+    def one_step():
+        eps_hat, eps_uncond = net_step(z, step)
+        ops.multistep_step(z, eps_hat, prev, coef, step, eps_uncond=eps_uncond, w_cfg=w_cfg or 0.0)
+        ops.step_inc(step)
+    loop = StepLoop(one_step, z, step.zero_, _NoStepNoise(), [[i] for i in range(coef.shape[0])], z, use_graph, return_all)
+    return loop.run("sampling:", 50, verbose)
+
+
+def multistep_loop(coef, z, net_out, return_all=False):
+    """The same update as a plain Python loop in torch fp32 (torch backend, CPU tensors): coef [n, 8] as above, net_out(i, z) the
+    network output at step i (the guided noise estimate / the velocity).  Returns z after the last step, or the stack of every step."""
+    c = coef.to(dtype=torch.float32, device="cpu")
+    prev, zs = None, []
+    for i in range(c.shape[0]):
+        e_z, e_e, w_z, w_x, w_p = (float(v) for v in c[i, :5])
+        est = e_z * z + e_e * net_out(i, z)
+        z = w_z * z + w_x * est
+        if w_p != 0.0:
+            z = z + w_p * prev
+        prev = est
+        if return_all:
+            zs.append(z)
+    return torch.stack(zs, dim=0) if return_all else z
 
 
 # ------------------------------------------------------------------------------------------------------------------ DDNM

@@ -19,13 +19,15 @@ On the HIP backend the training step is two kernels around the network: ``vdm_sf
 the step can be captured in a hipGraph (``trainer.GraphedTrainStep``; the times then come from the device step counter).  With
 ``VDM4CDM_EXPERIMENT=fused_head=0``, or a cube whose voxel count is no multiple of 4, the interpolation / target are the K7 kernel
 (``vdm_diffuse``: a x + b y per sample) and the loss and its gradient the K8 kernel: the same bits, launch by launch.  The Euler loop is
-the same captured hipGraph as the VDM sampler (``sampling.hip_graph_sampler``) with the coefficient table {1, -1/n, 0, t_i}.
+the same captured hipGraph as the VDM sampler (``sampling.hip_graph_sampler``) with the coefficient table {1, -1/n, 0, t_i};
+``sample(order=2)`` is Adams-Bashforth 2 after an Euler first step, x <- x + (1.5 v - 0.5 v_prev) / n, on the multistep loop
+(``sampling.hip_multistep_sampler``, kernel ``vdm_multistep_step``).
 """
 import torch
 import torch.nn as nn
 
 from . import _experiment
-from .sampling import ChainNoise, hip_graph_sampler
+from .sampling import ChainNoise, hip_graph_sampler, hip_multistep_sampler, multistep_loop
 from .vdm_model import _DiffusionLossFn, stratified_times
 
 # Fused head and loss of the HIP training step (vdm_sfm_head + vdm_sfm_loss; fused_head=0: diffuse -> (randn -> diffuse) -> diffuse ->
@@ -151,10 +153,37 @@ class SFM(nn.Module):
         return torch.stack([torch.ones(n, dtype=torch.float64), torch.full((n,), -1.0 / n, dtype=torch.float64),
                             torch.zeros(n, dtype=torch.float64), t], dim=1)
 
+    @staticmethod
+    def multistep_table(n, order=2):
+        """[n, 8] = {e_z = 0, e_e = 1, w_z = 1, w_x, w_p, t_i = i / n, 0, 0} for hip_multistep_sampler (K9m; the estimate is the
+        velocity itself).  Row 0, or every row with order=1, is explicit Euler (w_x = 1/n, w_p = 0); every other row Adams-Bashforth 2 on
+        the uniform grid: x <- x + (1.5 v - 0.5 v_prev) / n."""
+        if order not in (1, 2):
+            raise ValueError(f"multistep_table: order={order!r} (1 or 2)")
+        one, zero = torch.ones(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+        ab2 = torch.arange(n) >= (1 if order == 2 else n)
+        w_x = torch.where(ab2, 1.5 * one, one) / n
+        w_p = torch.where(ab2, -0.5 * one, zero) / n
+        return torch.stack([zero, one, one, w_x, w_p, torch.arange(n, dtype=torch.float64) / n, zero, zero], dim=1)
+
     @torch.no_grad()
-    def sample(self, x0, n_sampling_steps, v_conditionings=None, return_all=False, verbose=False, use_graph=True):
+    def sample(self, x0, n_sampling_steps, v_conditionings=None, return_all=False, verbose=False, use_graph=True, order=1):
+        """order=1: explicit Euler; order=2: Adams-Bashforth 2 after an Euler first step (one field of history, no extra network
+        evaluation)."""
+        if order not in (1, 2):
+            raise ValueError(f"sample: order={order!r} (1 or 2)")
         x0 = x0.to(torch.float32).contiguous()
         x = x0.clone()
+        if order == 2:
+            coef = self.multistep_table(n_sampling_steps, 2)
+            if self._hip(x):
+                s_cond = x0 if getattr(self.velocity_model, "s_conditioning_channels", 1) else None
+                return hip_multistep_sampler(self.velocity_model, x, coef.to(device=x.device, dtype=torch.float32).contiguous(), verbose,
+                                             use_graph, s_cond, list(v_conditionings or []), return_all=return_all)
+
+            def velocity(i, xt):
+                return self.velocity(xt, torch.full((xt.shape[0],), i / n_sampling_steps, device=xt.device), x0, v_conditionings)
+            return multistep_loop(coef, x, velocity, return_all)
         if self._hip(x) and not return_all:
             coef = self.step_table(n_sampling_steps).to(device=x.device, dtype=torch.float32).contiguous()
             s_cond = x0 if getattr(self.velocity_model, "s_conditioning_channels", 1) else None
@@ -231,11 +260,12 @@ class LightSFM(nn.Module):
             opt.register_step_post_hook(_after_step)
         return opt
 
-    def draw_samples(self, x0=None, n_sampling_steps=100, batch_size=None, verbose=False, return_all=False, **kwargs):
-        """Target-field samples for the source fields x0 (batch_size is implied by x0; accepted for the trainer's call)."""
+    def draw_samples(self, x0=None, n_sampling_steps=100, batch_size=None, verbose=False, return_all=False, order=1, **kwargs):
+        """Target-field samples for the source fields x0 (batch_size is implied by x0; accepted for the trainer's call).  order: 1
+        (Euler) or 2 (Adams-Bashforth 2), SFM.sample."""
         assert x0 is not None, "LightSFM.draw_samples needs the source field x0"
         return self.model.sample(x0.to(self.device), n_sampling_steps, v_conditionings=kwargs.get("v_conditionings"),
-                                 return_all=return_all, verbose=verbose, use_graph=kwargs.get("use_graph", True))
+                                 return_all=return_all, verbose=verbose, use_graph=kwargs.get("use_graph", True), order=order)
 
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
         out = {} if destination is None else destination

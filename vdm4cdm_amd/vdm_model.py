@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from . import _experiment
 from .sampling import ChainNoise, ddnm_lengths, ddnm_sample, ddnm_schedule, hip_ddnm_sampler, hip_graph_sampler  # noqa: F401
+from .sampling import check_sampler, hip_multistep_sampler, multistep_loop
 
 DATA_NOISE = 1.0e-3
 # Fused head of the HIP training step (vdm_diffuse_pack + vdm_loss_terms_rng; fused_head=0: randn -> diffuse -> pack_input, A/B)
@@ -425,17 +426,68 @@ class VDM(nn.Module):
         t_norm = (g_t - self.gamma_min) / (self.gamma_max - self.gamma_min)
         return torch.stack([a_s / a_t, c * s_t, s_s * torch.sqrt(c), t_norm], dim=1)
 
+    def multistep_table(self, n_sampling_steps, order=2, lower_order_final=True):
+        """Host fp64 table [n, 8] = {e_z, e_e, w_z, w_x, w_p, t_norm, 0, 0} of the deterministic multistep sampler (K9m), computed like
+        step_table on the same grid; row i goes from t = steps[i] to s = steps[i+1].  DPM-Solver++(2M) (Lu et al. 2022) with the data
+        prediction x_hat = (z - sigma_t eps_hat) / alpha_t = e_z z + e_e eps_hat as the modelled quantity: with lambda = log(alpha /
+        sigma) = -gamma / 2, h = lambda_s - lambda_t and B = alpha_s (1 - exp(-h)),
+            first order (DDIM):  z_s = (sigma_s / sigma_t) z + B x_hat
+            second order (2M):   z_s = (sigma_s / sigma_t) z + B ((1 + 1/(2r)) x_hat - (1/(2r)) x_hat_prev),   r = h_prev / h
+        Row 0 is first order (no history), every row with order=1, and the last row with lower_order_final (the usual guard of few-step
+        chains: the last step ends at the largest log-SNR).  A first-order row has w_p = 0 exactly."""
+        if order not in (1, 2):
+            raise ValueError(f"multistep_table: order={order!r} (1 or 2)")
+        n = n_sampling_steps
+        g = self._gamma_grid(n)
+        g_t, g_s = g[:-1], g[1:]
+        a_t, a_s = torch.sqrt(torch.sigmoid(-g_t)), torch.sqrt(torch.sigmoid(-g_s))
+        s_t, s_s = torch.sqrt(torch.sigmoid(g_t)), torch.sqrt(torch.sigmoid(g_s))
+        h = 0.5 * (g_t - g_s)                                # lambda_s - lambda_t
+        B = a_s * (-torch.expm1(-h))
+        second = torch.zeros(n, dtype=torch.bool)
+        if order == 2:
+            second[1:n - 1 if lower_order_final else n] = True
+        r = torch.ones_like(h)
+        r[1:] = h[:-1] / h[1:]                               # from the grid itself (fp32 linspace), not assumed to be 1
+        half = torch.where(second, 0.5 / r, torch.zeros_like(h))
+        t_norm = (g_t - self.gamma_min) / (self.gamma_max - self.gamma_min)
+        zero = torch.zeros_like(h)
+        return torch.stack([1.0 / a_t, -s_t / a_t, s_s / s_t, B * (1.0 + half), -B * half, t_norm, zero, zero], dim=1)
+
+    def _multistep_sample(self, z, n_sampling_steps, order, lower_order_final, return_all, verbose, use_graph, kwargs):
+        """The deterministic samplers ("ddim": order 1, "dpm2m": order 2) from z_1 = z: the device loop on the HIP backend, the same
+        table and update as a Python loop in torch fp32 otherwise."""
+        coef = self.multistep_table(n_sampling_steps, order, lower_order_final)
+        if self._hip(z):
+            cfg = self.w_cfg is not None and not self.training
+            assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+            return hip_multistep_sampler(self.score_model, z, coef.to(device=z.device, dtype=torch.float32).contiguous(), verbose,
+                                         use_graph, kwargs.get("s_conditioning"), list(kwargs.get("v_conditionings") or []),
+                                         w_cfg=float(self.w_cfg) if cfg else None, mask_fn=self.cfg_mask, return_all=return_all)
+        steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1, device=z.device)
+        return multistep_loop(coef, z, lambda i, zt: self.get_pred_noise(zt=zt, gamma_t=self.gamma(steps[i]), **kwargs), return_all)
+
     @torch.no_grad()
     def sample(self, batch_size, n_sampling_steps, device, z=None, return_all=False, verbose=False,
-               noises=None, seed=None, use_graph=True, seeds=None, **kwargs):
+               noises=None, seed=None, use_graph=True, seeds=None, sampler="ancestral", lower_order_final=True, **kwargs):
         """Ancestral sampling (notebook frame vdm_model.py:429-442).  `noises` (optional list of n tensors) and
         `seed` make a chain reproducible; on the HIP backend the step is a replayed hipGraph.
         `seeds` (one int per row): every row is a chain of its own, keyed by its seed wherever it sits in the batch - row r draws z_1
         and its step noise exactly as a batch-1 chain with seed=seeds[r] does (a supplied z: the seeds key the step noise only).
-        `seed` with batch_size > 1 keeps its meaning of one stream for the whole batch."""
+        `seed` with batch_size > 1 keeps its meaning of one stream for the whole batch.
+        `sampler`: "ancestral" (the default: the stochastic chain above), or a deterministic solver of the probability-flow ODE on the
+        same grid - "ddim" (first order) or "dpm2m" (DPM-Solver++(2M), second order, one field of history and no extra network
+        evaluation; multistep_table; `lower_order_final`: its last step is first order).  They draw no step noise: seed / seeds / z
+        key or supply z_1 exactly as above, noises= is an error.  Everything else in **kwargs goes to the network."""
+        check_sampler(sampler)
+        if sampler != "ancestral" and noises is not None:
+            raise ValueError(f"sample: noises= with sampler={sampler!r}: a deterministic sampler draws no step noise (z= supplies z_1)")
         noise = ChainNoise("sample", batch_size, self.score_model.shape, device, seed, seeds, noises)
         z = noise.z1(z)
-        if self._hip(z):                                     # (return_all: the same captured step, z copied out after every replay)
+        if sampler != "ancestral":
+            return self._multistep_sample(z, n_sampling_steps, 1 if sampler == "ddim" else 2, lower_order_final, return_all, verbose,
+                                          use_graph, kwargs)
+        if self._hip(z):                                   # (return_all: the same captured step, z copied out after every replay)
             coef = self.step_table(n_sampling_steps).to(device=z.device, dtype=torch.float32).contiguous()
             cfg = self.w_cfg is not None and not self.training
             assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
@@ -606,9 +658,11 @@ class LightVDM(nn.Module):
             g.set_state(state["noise_gen"])
             self.model._noise_gen, self.model._noise_gen_key = g, tuple(int(k) for k in state["noise_gen_key"])
 
-    def draw_samples(self, batch_size, n_sampling_steps=250, verbose=False, return_all=False, **kwargs):
+    def draw_samples(self, batch_size, n_sampling_steps=250, verbose=False, return_all=False, sampler="ancestral",
+                     lower_order_final=True, **kwargs):
+        """sampler: "ancestral" | "ddim" | "dpm2m" (VDM.sample)."""
         return self.model.sample(batch_size=batch_size, n_sampling_steps=n_sampling_steps, device=self.device,
-                                 verbose=verbose, return_all=return_all, **kwargs)
+                                 verbose=verbose, return_all=return_all, sampler=sampler, lower_order_final=lower_order_final, **kwargs)
 
     # state dict: {"model.score_model.<name>": tensor, "model.gamma_b": ..., ...}
     def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
