@@ -124,6 +124,30 @@ int vdm_conv_dgrad_gn(const vdm_conv_desc* d, const void* dout, const void* w_pa
 #define VDM_CONV_VARIANT_SPLIT 3 /* generic kernel, half-chunk workgroups (64-cout chunks on a small grid) */
 #define VDM_CONV_VARIANT_KSPLIT 4 /* deepest level: the waves of a workgroup split the K-blocks, one weight fetch per workgroup */
 int vdm_conv_kernel_variant(const vdm_conv_desc* d, int dgrad);
+/* The host-side plan vdm_conv_fwd (dgrad = 0) / vdm_conv_dgrad (dgrad = 1) follows for this descriptor (csrc/conv_common.h plan_of;
+ * host only, no HIP call): kernel family, packed-weight layout, channel blocking, spatial tile, whether the launch rolls up z and how
+ * it is segmented, and the launch grid.  Tests and profiling tools read it instead of restating the rules; vdm_conv_kernel_variant,
+ * vdm_conv_gn_tiles, vdm_conv_dgrad_gn_tiles and vdm_conv_packed_bytes answer from the same plan.  Returns VDM_OK, or the status the
+ * launch would return for the descriptor (VDM_ERR_UNSUPPORTED: an fp32 output of bf16 storage that is not built) with `out` filled. */
+#define VDM_CONV_CLS_UP_FWD 0   /* cls_kind of a VDM_CONV_VARIANT_CLASS plan: up-sampling conv forward (8 merged taps per class) */
+#define VDM_CONV_CLS_UP_DGRAD 1 /* its input gradient (one workgroup loops over the 8 classes) */
+#define VDM_CONV_CLS_S2_DGRAD 2 /* stride-2 conv, input gradient (1 / 2 / 4 / 8 taps per class) */
+typedef struct {
+    int32_t family;          /* VDM_CONV_VARIANT_*: the kernel */
+    int32_t layout;          /* VDM_CONV_VARIANT_GENERIC | _CLASS | _KPACK: the packed-weight layout */
+    int32_t cls_kind;        /* VDM_CONV_CLS_* when family is VDM_CONV_VARIANT_CLASS, else 0 */
+    int32_t nc;              /* 16-channel output tiles per packed chunk (SPLIT workgroups take half a chunk) */
+    int32_t nchunks;         /* output-channel chunks */
+    int32_t nkb;             /* reduction-channel blocks (32 channels bf16, 16 fp32) */
+    int32_t tz, ty;          /* spatial tile (x extent 16), of the coarse grid for the class kernels */
+    int32_t roll;            /* 1: rolling-z kernel (persistent workgroups walk up tile columns) */
+    int32_t nseg, zsteps;    /* rolling z: segments per tile column, z steps per segment (the last segment may be shorter); else 0 */
+    int32_t tiles;           /* per-sample tiles of the GroupNorm partials (vdm_conv_gn_tiles / vdm_conv_dgrad_gn_tiles) */
+    int32_t workgroups;      /* launch grid */
+    int32_t reserved;
+    size_t packed_bytes;     /* vdm_conv_packed_bytes of this direction */
+} vdm_conv_plan_info;
+int vdm_conv_plan(const vdm_conv_desc* d, int dgrad, vdm_conv_plan_info* out);
 
 /* dw[taps][cout][cin] (fp32) = sum over voxels; workspace holds per-workgroup partial slabs.
  * dbias (optional, ksize 3 only): dbias[cout] = sum over samples and voxels of dout (the conv bias gradient), computed

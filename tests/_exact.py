@@ -1,5 +1,5 @@
 """Helpers of the exact-integer kernel checks (tests/test_input_grad_kernels_gpu.py, tests/test_groupnorm_kernels_gpu.py,
-tests/test_wgrad_kernels_gpu.py, tests/test_attention_kernels_gpu.py): operands
+tests/test_wgrad_kernels_gpu.py, tests/test_conv_kernels_gpu.py, tests/test_attention_kernels_gpu.py; their CPU halves): operands
 that are small integers held as floats make every product and every partial sum an integer below 2^24, so fp32 addition is exact in
 any order and a kernel must give the bits of the same sum computed in int64 / float64 on the CPU."""
 import torch

@@ -20,6 +20,8 @@ CSRC = os.path.join(_HERE, "csrc")
 VDM_F32, VDM_BF16 = 0, 1
 PAD_ZEROS, PAD_CIRCULAR = 0, 1
 PACK_FWD, PACK_DGRAD = 0, 1
+CONV_GENERIC, CONV_CLASS, CONV_KPACK, CONV_SPLIT, CONV_KSPLIT = range(5)                                # VDM_CONV_VARIANT_*
+CLS_UP_FWD, CLS_UP_DGRAD, CLS_S2_DGRAD = range(3)                                                       # VDM_CONV_CLS_*
 WGRAD_THIN_IN, WGRAD_THIN_OUT, WGRAD_ROWS, WGRAD_ROWS_ROLL, WGRAD_TAPSPLIT, WGRAD_CLASS = range(6)      # VDM_WGRAD_*
 GN_STATS_WS_BYTES = 2048 * 2 * 64 * 4
 
@@ -52,6 +54,12 @@ class GnFold(C.Structure):
 class WgradPlanInfo(C.Structure):
     """vdm_wgrad_plan_info"""
     _fields_ = [(k, C.c_int32) for k in ("kernel", "tz", "ty", "workgroups", "tiles", "P")] + [("workspace_bytes", C.c_size_t)]
+
+
+class ConvPlanInfo(C.Structure):
+    """vdm_conv_plan_info"""
+    _fields_ = [(k, C.c_int32) for k in ("family", "layout", "cls_kind", "nc", "nchunks", "nkb", "tz", "ty", "roll", "nseg", "zsteps", "tiles",
+                                         "workgroups", "reserved")] + [("packed_bytes", C.c_size_t)]
 
 
 class CondMlp(C.Structure):
@@ -98,6 +106,7 @@ SIGNATURES = {
     "vdm_conv_dgrad_gn_tiles": (_i, [_D]),
     "vdm_conv_dgrad_gn": (_i, [_D, _p, _p, _p, C.POINTER(GnFold), _p]),
     "vdm_conv_kernel_variant": (_i, [_D, _i]),
+    "vdm_conv_plan": (_i, [_D, _i, C.POINTER(ConvPlanInfo)]),
     "vdm_conv_wgrad_workspace_bytes": (_sz, [_D]),
     "vdm_conv_wgrad": (_i, [_D, _p, _p, _p, _p, _i, _p, _sz, _p]),
     "vdm_conv_wgrad_plan": (_i, [_D, _i, _i, C.POINTER(WgradPlanInfo)]),

@@ -217,6 +217,33 @@ extern "C" int vdm_conv_kernel_variant(const vdm_conv_desc* d, int dgrad) {
     return validate(d) ? -1 : plan_of(d, dgrad).family;
 }
 
+extern "C" int vdm_conv_plan(const vdm_conv_desc* d, int dgrad, vdm_conv_plan_info* out) {
+    int e = validate(d);
+    if (e) return e;
+    VDM_REQUIRE(out, "conv_plan: NULL pointer");
+    const Plan p = plan_of(d, dgrad != 0);
+    const long long nwg = plan_workgroups(p);
+    out->family = p.family; out->layout = p.layout; out->cls_kind = p.cls_kind;
+    out->nc = p.nc; out->nchunks = p.nchunks; out->nkb = p.nkb;
+    out->tz = p.tz; out->ty = p.ty;
+    out->roll = p.roll; out->nseg = p.nseg; out->zsteps = p.zsteps;
+    out->tiles = p.tiles;
+    out->workgroups = (int32_t)(nwg < 0x7fffffffLL ? nwg : 0x7fffffffLL);
+    out->reserved = 0;
+    out->packed_bytes = p.packed_bytes;
+    // the descriptor-level refusals of vdm_conv_fwd (launch_fwd, the class branch of vdm_conv_fwd)
+    if (nwg > 0x7fffffffLL) { set_error("conv: grid too large"); return VDM_ERR_ARG; }
+    if (p.out_f32 && p.family == VDM_CONV_VARIANT_CLASS) {
+        set_error("conv_fwd: the up-sampling conv takes no per-sample bias / fp32 output");
+        return VDM_ERR_ARG;
+    }
+    if (p.out_f32 && p.dtype == VDM_BF16 && !(p.ks == 3 && p.stride == 1 && !p.ups && p.nc == 1)) {
+        set_error("conv: out_f32 with bf16 input is only built for ksize 3, stride 1, cout <= 16");
+        return VDM_ERR_UNSUPPORTED;
+    }
+    return VDM_OK;
+}
+
 // largest workspace over the (want_bias, accumulate) combinations: they change which kernel serves a descriptor
 extern "C" size_t vdm_conv_wgrad_workspace_bytes(const vdm_conv_desc* d) {
     if (validate(d) != VDM_OK) return 0;

@@ -1331,6 +1331,16 @@ static Plan plan_of(const vdm_conv_desc* d, int dgrad) {     // d has passed val
     return p;
 }
 
+// workgroups the launcher of the plan's family starts (launch_fwd_cfg, launch_roll, launch_ksplit, launch_kpack, launch_cls_cfg): one per
+// (sample, output-channel chunk, spatial tile) - half chunks double them, the rolling-z kernel starts one per column segment instead of
+// one per z tile, and the class kernels that scatter to the fine grid (up-sampling forward, stride-2 dgrad) one per parity class
+static long long plan_workgroups(const Plan& p) {
+    const long long cols = (long long)cdiv(p.Dy, p.ty) * cdiv(p.Dx, 16);
+    const long long spatial = cols * (p.roll ? p.nseg : cdiv(p.Dz, p.tz));
+    const int mult = p.family == VDM_CONV_VARIANT_SPLIT ? 2 : (p.family == VDM_CONV_VARIANT_CLASS && p.cls_kind != CLS_UP_DGRAD ? 8 : 1);
+    return (long long)p.N * p.nchunks * spatial * mult;
+}
+
 static void fill_dims(ConvArgs& a, const vdm_conv_desc* d) {
     a.N = d->n; a.Dz = d->od; a.Dy = d->oh; a.Dx = d->ow;
     a.Iz = d->od * d->stride; a.Iy = d->oh * d->stride; a.Ix = d->ow * d->stride;
