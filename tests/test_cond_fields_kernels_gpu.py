@@ -2,9 +2,12 @@
 through its hip_ops wrapper: vdm_pack_fields, vdm_diffuse_pack_fields, vdm_conv_in_dgrad_fields, and conv_in itself (forward and weight
 gradient of the generic conv kernels at cin = 3, 4).
 
-The checkers are never the code under test: the single-field entries of the parent ABI (pack_input, diffuse_pack, conv_in_dgrad: bit
-equality where the new entry restates them), float64 torch on the CPU (exact-integer check A, random-data check B with the bound of
-tests/test_input_grad_kernels_gpu.py) and sentinel buffers around the outputs.
+The checkers are never the code under test: pack_input (a separate kernel), float64 torch on the CPU (exact-integer check A, random-
+data check B with the bound of tests/test_input_grad_kernels_gpu.py) and sentinel buffers around the outputs.  The single-field entries
+diffuse_pack and conv_in_dgrad launch the kernels of the _fields entries (one head kernel, one K1t kernel): bit equality with them says
+that the two entries hand the kernel the same arguments; at K = 1 and cin <= 2 both sides run the same instantiation, which is not an
+independent check - those come from test_diffuse_pack_fields_exact_integers and the float64 K1t checks of
+tests/test_input_grad_kernels_gpu.py.
 """
 import pytest
 import torch
@@ -89,7 +92,9 @@ def _head_inputs(n, k, per, seed):
 @pytest.mark.parametrize("noise", ["supplied", "in_kernel"])
 def test_diffuse_pack_fields_equals_diffuse_pack(noise, k, dtype, per):
     """z_t, packed channel 0 and channel 1 equal diffuse_pack(x, c_0, ...) bit for bit (the same Philox counters, the same rounding);
-    channels 2.. equal pack_fields; with z_t = None the packed output does not change."""
+    channels 2.. equal pack_fields; with z_t = None the packed output does not change.  Both entries launch the one head kernel: at
+    k1 the two sides run the same instantiation (the entries' argument mapping is what is compared), at k2 / k3 sibling instantiations;
+    the independent reference is test_diffuse_pack_fields_exact_integers."""
     _lib, ops = _mods()
     n = 3 if per < 1000 else 2
     x, cond, eps, al, si = _head_inputs(n, k, per, 10 * k + per % 97)
@@ -103,6 +108,56 @@ def test_diffuse_pack_fields_equals_diffuse_pack(noise, k, dtype, per):
     assert torch.equal(_bits(packed[..., 2:]), _bits(plain[..., 2:])), "channels 2.. differ from vdm_pack_fields"
     none, packed0 = ops.diffuse_pack_fields(x, cond, al, si, dtype, want_z=False, **kw)
     assert none is None and torch.equal(_bits(packed0), _bits(packed))
+
+
+HEAD_CONST = (1.0, 0.5, 2.0, 1.5, 0.25)               # alpha / sigma of the exact check: powers of two or 1.5
+HEAD_A_SHAPES = [(3, 4), (3, 260), (2, 16 * 16 * 16 + 4)]      # one lane; ragged against the 256-voxel round; several rounds + a one-lane tail
+
+
+def _nan_framed(t):
+    """`t` on the device in the middle of a NaN-filled buffer: a read before or behind the operand poisons the result."""
+    _, v, _ = in_sentinel(t.numel(), tuple(t.shape), value=float("nan"))
+    v.copy_(t)
+    return v
+
+
+@pytest.mark.parametrize("shape", HEAD_A_SHAPES, ids=[f"n{n}_per{p}" for n, p in HEAD_A_SHAPES])
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("k", [2, 3], ids=["k2", "k3"])
+def test_diffuse_pack_fields_exact_integers(k, dtype, shape):
+    """A reference that is no sibling instantiation of the head kernel: x, eps and the K planes uniform in {-2..2}, alpha and sigma in
+    {1, 0.5, 2, 1.5, 0.25}, so alpha x + sigma eps is a multiple of 1/4 of magnitude <= 8 - exact in fp32 in any order and rounding,
+    and exact in bf16 (6 significant bits at the most).  z_t must have the bits of the float64 expression and every byte of the piece
+    {z_t, c_0 .. c_{K-1}, 0 ...} those of the reference in the storage type, with and without z_t; the inputs sit in NaN frames, the
+    outputs inside sentinels (the C entry directly: the wrapper allocates its outputs)."""
+    _lib, ops = _mods()
+    n, per = shape
+    epl = ops.cpad(1 + k, dtype)
+    x, eps, cond = ints((n, per), 31, terms=4), ints((n, per), 32, terms=4), ints((n, k, per), 33, terms=4)
+    al = torch.tensor([HEAD_CONST[i % 5] for i in range(n)])
+    si = torch.tensor([HEAD_CONST[(i + 2) % 5] for i in range(n)])
+    zref = al.double()[:, None] * x.double() + si.double()[:, None] * eps.double()
+    assert zref.abs().max() <= 8 and torch.equal(zref * 4, (zref * 4).round())
+    ref = torch.zeros((n, per, epl), dtype=dtype)
+    ref[..., 0] = zref.to(dtype)
+    ref[..., 1:1 + k] = cond.permute(0, 2, 1).to(dtype)
+    assert torch.equal(ref[..., 0].double(), zref), "the storage type does not hold z_t exactly"
+    ity = torch.int16 if dtype == torch.bfloat16 else torch.int32
+    xd, ed, cd, ald, sid = _nan_framed(x), _nan_framed(eps), _nan_framed(cond), _nan_framed(al), _nan_framed(si)
+    for with_z in (True, False):
+        _, packed, p_ok = in_sentinel(n * per * epl, (n, per, epl), dtype=dtype)
+        z_buf, z, z_ok = in_sentinel(n * per, (n, per))
+        _lib.check(_lib.lib().vdm_diffuse_pack_fields(xd.data_ptr(), cd.data_ptr(), k, ed.data_ptr(), 0, 0, None, ald.data_ptr(), sid.data_ptr(), n,
+                                                      per, ops.dt_id(dtype), z.data_ptr() if with_z else None, packed.data_ptr(), None),
+                   "vdm_diffuse_pack_fields")
+        torch.cuda.synchronize()
+        assert p_ok() and z_ok(), "diffuse_pack_fields wrote outside packed / z_t"
+        bad = (packed.view(ity) != ref.to(DEV).view(ity)).nonzero()
+        assert bad.shape[0] == 0, f"packed z_t={with_z}: {bad.shape[0]} elements differ in their bytes; first at {bad[:8].tolist()}"
+        if with_z:
+            assert_same_bits(z, zref, "diffuse_pack_fields z_t")
+        else:
+            assert bool((z_buf == -7777.0).all()), "z_t was written without being asked for"
 
 
 def test_diffuse_pack_fields_with_a_seed_step_counter():
@@ -224,7 +279,9 @@ def test_k1t_fields_random_against_float64(case):
 @pytest.mark.parametrize("circular", [False, True], ids=["zeros", "circ"])
 @pytest.mark.parametrize("cin", [1, 2])
 def test_k1t_fields_equals_the_single_field_entry(cin, circular, dtype):
-    """cin in {1, 2}: the bits of vdm_conv_in_dgrad on random data (the same summation order)."""
+    """cin in {1, 2}: the bits of vdm_conv_in_dgrad on random data.  Both entries launch the same instantiation of the one K1t kernel,
+    so this compares their argument mapping (ds [n][1][vol] = [n][vol]); vdm_conv_in_dgrad's independent reference is float64
+    (tests/test_input_grad_kernels_gpu.py)."""
     _lib, ops = _mods()
     for k, (n, grid, C) in enumerate([(3, (5, 7, 18), 48), (1, (1, 5, 3), 16), (2, (3, 4, 33), 64)]):
         dh = rnd((n,) + grid + (C,), 40 + k, dtype).to(dtype).to(DEV)

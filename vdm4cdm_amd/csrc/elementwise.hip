@@ -604,78 +604,27 @@ __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused head of the training step (K7 + the input packing of conv_in): z_t = alpha[n] x + sigma[n] eps with eps drawn IN the kernel
-// (Philox, the counters of randn_kernel: same (seed, stream id, element group) -> the same field vdm_randn would have written) or
-// read (supplied noise: parity tests), written once as fp32 (optional) and once as the NDHWC input of conv_in
-// [z_t, s_conditioning, 0 ...] in the compute dtype - randn + diffuse + pack_input in one pass over x.
-// A thread owns 4 consecutive voxels (one Philox call); the 16-byte pieces of the packed tensor are re-dealt inside the wave so
-// that every store instruction writes 1 KiB contiguously (lane L stores piece 64 r + L of the wave's 256 in round r).
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) diffuse_pack_kernel(const float* __restrict__ x, const float* __restrict__ sc, const float* __restrict__ eps,
-                                                          uint64_t seed0, uint64_t sid, const int32_t* __restrict__ seed_step,
-                                                          const float* __restrict__ alpha, const float* __restrict__ sigma, int64_t per,
-                                                          float* __restrict__ z, T* __restrict__ packed, int blocks_per_n) {
-    constexpr int EPL = DT<T>::EPL;
-    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
-    const uint64_t seed = mix_seed(seed0, seed_step);
-    const float al = alpha[n], si = sigma[n];
-    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
-    const size_t base = (size_t)n * per;
-    const float4* x4 = reinterpret_cast<const float4*>(x + base);
-    const float4* s4 = sc ? reinterpret_cast<const float4*>(sc + base) : nullptr;
-    const float4* e4 = eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
-    float4* z4 = z ? reinterpret_cast<float4*>(z + base) : nullptr;
-    const int lane = threadIdx.x & 63;
-    const int src0 = lane >> 2, comp = lane & 3;
-    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform trip count: the
-    for (int64_t it = 0; it < rounds; ++it) {                                                           // shuffles need every lane
-        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
-        const bool ok = i < n4;
-        const int64_t ic = ok ? i : n4 - 1;
-        const float4 xv = x4[ic];
-        const float4 sv = s4 ? s4[ic] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 ev = e4 ? e4[ic] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + ic));
-        const float zz[4] = {al * xv.x + si * ev.x, al * xv.y + si * ev.y, al * xv.z + si * ev.z, al * xv.w + si * ev.w};
-        const float ss[4] = {sv.x, sv.y, sv.z, sv.w};
-        if (z4 && ok) z4[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
-        const int64_t wave_g0 = i - lane;                            // first group of this wave (lane 0's)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int src = 16 * r + src0;
-            float zr = 0.f, sr = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float a = __shfl(zz[k], src, 64), b = __shfl(ss[k], src, 64);
-                if (k == comp) { zr = a; sr = b; }
-            }
-            const int64_t vox = 4 * wave_g0 + 64 * r + lane;        // voxel inside the sample
-            if (vox < per) {
-                Piece<T> pc;
-#pragma unroll
-                for (int j = 0; j < EPL; ++j) pc.f[j] = 0.f;
-                pc.f[0] = zr; pc.f[1] = sr;
-                *reinterpret_cast<uint4*>(packed + (base + (size_t)vox) * EPL) = pc.store();
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K conditioning fields (ABI v18): conv_in's packed input {z, c_0 .. c_{K-1}, 0 ...} - still ONE 16-byte piece per voxel in both storage
-// types (1 + K <= 4).  cond is NCDHW [n][K][per].  Same ownership and re-deal as diffuse_pack_kernel: a thread loads float4 (4 consecutive
-// voxels) from each of the 1 + K planes, lane L of a wave stores piece 64 r + L of the wave's 256 in round r (1 KiB per store instruction).
+// Head of the network: the NDHWC input of conv_in {z, c_0 .. c_{K-1}, 0 ...} in the compute dtype, written in the pass that makes z -
+// ONE 16-byte piece per voxel in both storage types (1 + K <= 4, K = 0 .. 3 conditioning planes).  One skeleton, head_kernel, and three
+// sources of what a thread owns (4 consecutive voxels: the four values zz of channel 0 and cc of the K planes):
+//   PlainSrc    vdm_pack_fields                            z and cond [n][K][per] as they are (ABI v18)
+//   DiffuseSrc  vdm_diffuse_pack, vdm_diffuse_pack_fields  z_t = alpha[n] x + sigma[n] eps, the bits of diffuse_kernel (ABI v11, v18)
+//   FlowSrc     vdm_sfm_head                               x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps), the plane cond ? x0 : 0 (ABI v21)
+// eps is drawn IN the kernel (Philox, the counters of randn_kernel: same (seed, stream id, element group) -> the same field vdm_randn
+// would have written) or read (supplied noise: parity tests).  z is also written as fp32 where it is asked for: randn + diffuse +
+// pack_input in one pass over x.  The 16-byte pieces of the packed tensor are re-dealt inside the wave so that every store instruction
+// writes 1 KiB contiguously (lane L stores piece 64 r + L of the wave's 256 in round r).
 // ---------------------------------------------------------------------------------------------
 template <typename T, int K>
-__device__ __forceinline__ void deal_pieces(const float (&zz)[4], const float (&cc)[K][4], int lane, int64_t wave_g0, int64_t per,
+__device__ __forceinline__ void deal_pieces(const float (&zz)[4], const float (&cc)[K > 0 ? K : 1][4], int lane, int64_t wave_g0, int64_t per,
                                             T* __restrict__ packed_n) {
     constexpr int EPL = DT<T>::EPL;
-    static_assert(1 + K <= EPL && 1 + K <= 4, "one 16-byte piece per voxel");
+    static_assert(K >= 0 && 1 + K <= EPL && 1 + K <= 4, "one 16-byte piece per voxel");
     const int src0 = lane >> 2, comp = lane & 3;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int src = 16 * r + src0;
-        float zr = 0.f, cr[K];
+        float zr = 0.f, cr[K > 0 ? K : 1];
 #pragma unroll
         for (int f = 0; f < K; ++f) cr[f] = 0.f;
 #pragma unroll
@@ -701,68 +650,95 @@ __device__ __forceinline__ void deal_pieces(const float (&zz)[4], const float (&
     }
 }
 
-template <typename T, int K>
-__global__ void __launch_bounds__(256) pack_fields_kernel(const float* __restrict__ z, const float* __restrict__ cond, int64_t per,
-                                                         T* __restrict__ packed, int blocks_per_n) {
+// src (by value: a block's own copy) is moved to sample n by seek, then load gives zz and cc of float4 group ic of that sample.
+template <typename T, int K, typename Src>
+__global__ void __launch_bounds__(256) head_kernel(Src src, int64_t per, float* __restrict__ z, T* __restrict__ packed, int blocks_per_n) {
     constexpr int EPL = DT<T>::EPL;
     const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
-    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
-    const float4* z4 = reinterpret_cast<const float4*>(z + (size_t)n * per);
-    const float4* c4 = reinterpret_cast<const float4*>(cond + (size_t)n * K * per);
-    const int lane = threadIdx.x & 63;
-    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform: the shuffles need every lane
-    for (int64_t it = 0; it < rounds; ++it) {
-        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
-        const int64_t ic = i < n4 ? i : n4 - 1;
-        const float4 zv = z4[ic];
-        const float zz[4] = {zv.x, zv.y, zv.z, zv.w};
-        float cc[K][4];
-#pragma unroll
-        for (int f = 0; f < K; ++f) {
-            const float4 cv = c4[(size_t)f * n4 + ic];
-            cc[f][0] = cv.x; cc[f][1] = cv.y; cc[f][2] = cv.z; cc[f][3] = cv.w;
-        }
-        deal_pieces<T, K>(zz, cc, lane, i - lane, per, packed + (size_t)n * per * EPL);
-    }
-}
-
-// diffuse_pack_kernel for K conditioning planes: the same Philox counters and the same z_t expression, so z_t and channel 0 carry the
-// bits vdm_diffuse_pack gives for the same arguments.
-template <typename T, int K>
-__global__ void __launch_bounds__(256) diffuse_pack_fields_kernel(const float* __restrict__ x, const float* __restrict__ cond,
-                                                                 const float* __restrict__ eps, uint64_t seed0, uint64_t sid,
-                                                                 const int32_t* __restrict__ seed_step, const float* __restrict__ alpha,
-                                                                 const float* __restrict__ sigma, int64_t per, float* __restrict__ z,
-                                                                 T* __restrict__ packed, int blocks_per_n) {
-    constexpr int EPL = DT<T>::EPL;
-    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
-    const uint64_t seed = mix_seed(seed0, seed_step);
-    const float al = alpha[n], si = sigma[n];
     const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
     const size_t base = (size_t)n * per;
-    const float4* x4 = reinterpret_cast<const float4*>(x + base);
-    const float4* c4 = reinterpret_cast<const float4*>(cond + base * K);
-    const float4* e4 = eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
+    src.template seek<K>(n, per);
     float4* z4 = z ? reinterpret_cast<float4*>(z + base) : nullptr;
     const int lane = threadIdx.x & 63;
-    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);
-    for (int64_t it = 0; it < rounds; ++it) {
+    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform trip count: the
+    for (int64_t it = 0; it < rounds; ++it) {                                                           // shuffles need every lane
         const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
         const bool ok = i < n4;
-        const int64_t ic = ok ? i : n4 - 1;
-        const float4 xv = x4[ic];
-        const float4 ev = e4 ? e4[ic] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + ic));
-        const float zz[4] = {al * xv.x + si * ev.x, al * xv.y + si * ev.y, al * xv.z + si * ev.z, al * xv.w + si * ev.w};
-        float cc[K][4];
-#pragma unroll
-        for (int f = 0; f < K; ++f) {
-            const float4 cv = c4[(size_t)f * n4 + ic];
-            cc[f][0] = cv.x; cc[f][1] = cv.y; cc[f][2] = cv.z; cc[f][3] = cv.w;
-        }
+        const int64_t ic = ok ? i : n4 - 1;                          // (nothing is read outside the inputs)
+        float zz[4], cc[K > 0 ? K : 1][4];
+        src.template load<K>(n4, ic, zz, cc);
         if (z4 && ok) z4[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
         deal_pieces<T, K>(zz, cc, lane, i - lane, per, packed + base * EPL);
     }
 }
+
+__device__ __forceinline__ void ld4(const float* p, int64_t i, float (&v)[4]) {
+    const float4 q = reinterpret_cast<const float4*>(p)[i];
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+}
+
+template <int K>
+__device__ __forceinline__ void ld_planes(const float* cond_n, int64_t n4, int64_t ic, float (&cc)[K > 0 ? K : 1][4]) {
+#pragma unroll
+    for (int f = 0; f < K; ++f) ld4(cond_n, (int64_t)f * n4 + ic, cc[f]);
+}
+
+// eps of group ic of a sample whose first group is g0 in the batch: read, or drawn when eps_n is NULL
+__device__ __forceinline__ void ld_eps(const float* eps_n, uint64_t seed, uint64_t sid, uint64_t g0, int64_t ic, float (&e)[4]) {
+    if (eps_n) {
+        ld4(eps_n, ic, e);
+    } else {
+        const float4 r = randn4(seed, sid, g0 + (uint64_t)ic);
+        e[0] = r.x; e[1] = r.y; e[2] = r.z; e[3] = r.w;
+    }
+}
+
+// al * x + si * e as -ffp-contract=fast contracts it in diffuse_kernel: the first product is fused, the second rounded
+__device__ __forceinline__ float diffuse_fma(float al, float x, float si, float e) { return fmaf(al, x, uncontracted_mul(si, e)); }
+
+struct PlainSrc {
+    static constexpr int KMIN = 1, KMAX = 3;
+    const float *z, *cond;
+    template <int K>
+    __device__ __forceinline__ void seek(int n, int64_t per) {
+        z += (size_t)n * per;
+        cond += (size_t)n * K * per;
+    }
+    template <int K>
+    __device__ __forceinline__ void load(int64_t n4, int64_t ic, float (&zz)[4], float (&cc)[K > 0 ? K : 1][4]) const {
+        ld4(z, ic, zz);
+        ld_planes<K>(cond, n4, ic, cc);
+    }
+};
+
+struct DiffuseSrc {
+    static constexpr int KMIN = 0, KMAX = 3;
+    const float *x, *cond, *eps;                                    // cond: unused at K = 0; eps: NULL = drawn
+    uint64_t seed, sid;
+    const int32_t* seed_step;
+    const float *alpha, *sigma;
+    float al, si;                                                   // of the sample (seek)
+    uint64_t g0;
+    template <int K>
+    __device__ __forceinline__ void seek(int n, int64_t per) {
+        const size_t base = (size_t)n * per;
+        x += base;
+        if (K > 0) cond += base * K;
+        if (eps) eps += base;
+        seed = mix_seed(seed, seed_step);
+        al = alpha[n]; si = sigma[n];
+        g0 = (uint64_t)((int64_t)n * (per >> 2));
+    }
+    template <int K>
+    __device__ __forceinline__ void load(int64_t n4, int64_t ic, float (&zz)[4], float (&cc)[K > 0 ? K : 1][4]) const {
+        float xv[4], ev[4];
+        ld4(x, ic, xv);
+        ld_eps(eps, seed, sid, g0, ic, ev);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) zz[j] = diffuse_fma(al, xv[j], si, ev[j]);
+        ld_planes<K>(cond, n4, ic, cc);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // Flow matching (ABI v21): the head and the loss of an SFM training step.  Their arithmetic is pinned, bit for bit, to the chain of
@@ -773,7 +749,7 @@ __global__ void __launch_bounds__(256) diffuse_pack_fields_kernel(const float* _
 //   sfm_sq4    : loss_terms_rng_kernel's (d0 d0 + d1 d1) + (d2 d2 + d3 d3) = fma(d0, d0, d1 * d1) + fma(d2, d2, d3 * d3)
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float sfm_interp(float t, float omt, float x0, float x1, bool noisy, float sigma, float e) {
-    const float xt = fmaf(t, x1, uncontracted_mul(omt, x0));
+    const float xt = diffuse_fma(t, x1, omt, x0);
     return noisy ? xt + uncontracted_mul(sigma, e) : xt;
 }
 
@@ -781,43 +757,43 @@ __device__ __forceinline__ float sfm_sq4(float d0, float d1, float d2, float d3)
     return fmaf(d0, d0, uncontracted_mul(d1, d1)) + fmaf(d2, d2, uncontracted_mul(d3, d3));
 }
 
-// Head: x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps), written once as fp32 (optional) and once as conv_in's packed input
-// {x_t, cond ? x0 : 0, 0 ...} - diffuse + (randn + diffuse) + pack_input in one pass.  Ownership and re-deal of diffuse_pack_kernel: a
-// thread owns 4 consecutive voxels (one Philox call, the counters of randn_kernel), deal_pieces stores 1 KiB per instruction.
-// sigma == 0 (uniform): neither eps nor the generator is touched.
-template <typename T>
-__global__ void __launch_bounds__(256) sfm_head_kernel(const float* __restrict__ x0, const float* __restrict__ x1, const float* __restrict__ eps,
-                                                      uint64_t seed0, uint64_t sid, const int32_t* __restrict__ seed_step,
-                                                      const float* __restrict__ t, float sigma, int cond, int64_t per,
-                                                      float* __restrict__ x_t, T* __restrict__ packed, int blocks_per_n) {
-    constexpr int EPL = DT<T>::EPL;
-    const int n = blockIdx.x / blocks_per_n, bn = blockIdx.x % blocks_per_n;
-    const bool noisy = sigma > 0.f;
-    const uint64_t seed = noisy && !eps ? mix_seed(seed0, seed_step) : 0;
-    const float tn = t[n], omt = 1.0f - tn;                        // (1 - t rounded to fp32 first, as the chain's host expression)
-    const int64_t n4 = per >> 2;                                   // (host: per % 4 == 0)
-    const size_t base = (size_t)n * per;
-    const float4* a4 = reinterpret_cast<const float4*>(x0 + base);
-    const float4* b4 = reinterpret_cast<const float4*>(x1 + base);
-    const float4* e4 = noisy && eps ? reinterpret_cast<const float4*>(eps + base) : nullptr;
-    float4* z4 = x_t ? reinterpret_cast<float4*>(x_t + base) : nullptr;
-    const int lane = threadIdx.x & 63;
-    const int64_t rounds = (n4 + (int64_t)blocks_per_n * 256 - 1) / ((int64_t)blocks_per_n * 256);      // uniform: the shuffles need every lane
-    for (int64_t it = 0; it < rounds; ++it) {
-        const int64_t i = (it * blocks_per_n + bn) * 256 + threadIdx.x;
-        const bool ok = i < n4;
-        const int64_t ic = ok ? i : n4 - 1;
-        const float4 av = a4[ic], bv = b4[ic];
-        float4 ev = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (noisy) ev = e4 ? e4[ic] : randn4(seed, sid, (uint64_t)((int64_t)n * n4 + ic));
-        const float zz[4] = {sfm_interp(tn, omt, av.x, bv.x, noisy, sigma, ev.x), sfm_interp(tn, omt, av.y, bv.y, noisy, sigma, ev.y),
-                             sfm_interp(tn, omt, av.z, bv.z, noisy, sigma, ev.z), sfm_interp(tn, omt, av.w, bv.w, noisy, sigma, ev.w)};
-        float cc[1][4] = {{0.f, 0.f, 0.f, 0.f}};
-        if (cond) { cc[0][0] = av.x; cc[0][1] = av.y; cc[0][2] = av.z; cc[0][3] = av.w; }
-        if (z4 && ok) z4[i] = make_float4(zz[0], zz[1], zz[2], zz[3]);
-        deal_pieces<T, 1>(zz, cc, lane, i - lane, per, packed + base * EPL);
+// Head source: x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps) and the plane cond ? x0 : 0 - diffuse + (randn + diffuse) + pack_input in
+// one pass.  sigma == 0 (uniform), or eps supplied: neither the generator nor seed_step is touched.
+struct FlowSrc {
+    static constexpr int KMIN = 1, KMAX = 1;
+    const float *x0, *x1, *eps;
+    uint64_t seed, sid;
+    const int32_t* seed_step;
+    const float* t;
+    float sigma;
+    int cond;
+    float tn, omt;                                                  // of the sample (seek)
+    uint64_t g0;
+    template <int K>
+    __device__ __forceinline__ void seek(int n, int64_t per) {
+        const size_t base = (size_t)n * per;
+        x0 += base; x1 += base;
+        const bool noisy = sigma > 0.f;
+        seed = noisy && !eps ? mix_seed(seed, seed_step) : 0;
+        eps = noisy && eps ? eps + base : nullptr;
+        tn = t[n]; omt = 1.0f - tn;                                 // (1 - t rounded to fp32 first, as the chain's host expression)
+        g0 = (uint64_t)((int64_t)n * (per >> 2));
     }
-}
+    template <int K>
+    __device__ __forceinline__ void load(int64_t n4, int64_t ic, float (&zz)[4], float (&cc)[1][4]) const {
+        static_assert(K == 1, "one plane: x0 or +0");
+        const bool noisy = sigma > 0.f;
+        float av[4], bv[4], ev[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(x0, ic, av);
+        ld4(x1, ic, bv);
+        if (noisy) ld_eps(eps, seed, sid, g0, ic, ev);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            zz[j] = sfm_interp(tn, omt, av[j], bv[j], noisy, sigma, ev[j]);
+            cc[0][j] = cond ? av[j] : 0.f;
+        }
+    }
+};
 
 // Loss: part[block] = sum (v_hat - (x1 - x0))^2 and d_v = coef[n] (v_hat - (x1 - x0)); the target field is never written.  The residual,
 // the per-thread accumulation and the block fold are those of loss_terms_rng_kernel's first sum on the materialised target (x1 - x0 is
@@ -1399,6 +1375,31 @@ extern "C" int vdm_loss_terms(const float* x, const float* eps, const float* eps
     return VDM_OK;
 }
 
+// The one launcher of head_kernel: dtype x K for the source's entries (which have refused every k outside KMIN .. KMAX).
+template <typename T, int K, typename Src>
+static void launch_head_k(const Src& src, int n, int64_t per, float* z, void* packed, hipStream_t s) {
+    if constexpr (K >= Src::KMIN && K <= Src::KMAX) {
+        const int bpn = bpn_for(per / 4, n);
+        hipLaunchKernelGGL((head_kernel<T, K, Src>), dim3(bpn * n), dim3(256), 0, s, src, per, z, (T*)packed, bpn);
+    }
+}
+
+template <typename T, typename Src>
+static void launch_head_t(const Src& src, int k, int n, int64_t per, float* z, void* packed, hipStream_t s) {
+    if (k == 0) launch_head_k<T, 0>(src, n, per, z, packed, s);
+    else if (k == 1) launch_head_k<T, 1>(src, n, per, z, packed, s);
+    else if (k == 2) launch_head_k<T, 2>(src, n, per, z, packed, s);
+    else launch_head_k<T, 3>(src, n, per, z, packed, s);
+}
+
+template <typename Src>
+static int launch_head(const Src& src, int k, int n, int64_t per, int dtype, float* z, void* packed, void* stream) {
+    if (dtype == VDM_F32) launch_head_t<float>(src, k, n, per, z, packed, (hipStream_t)stream);
+    else launch_head_t<bf16_t>(src, k, n, per, z, packed, (hipStream_t)stream);
+    VDM_LAUNCH_CHECK("head_kernel");
+    return VDM_OK;
+}
+
 extern "C" int vdm_diffuse_pack(const float* x, const float* s_cond, const float* eps, uint64_t seed, uint64_t stream_id,
                                 const int32_t* seed_step, const float* alpha, const float* sigma, int n, int64_t per, int dtype, float* z_t,
                                 void* packed, void* stream) {
@@ -1406,23 +1407,8 @@ extern "C" int vdm_diffuse_pack(const float* x, const float* s_cond, const float
     VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "diffuse_pack: bad dtype %d", dtype);
     VDM_REQUIRE((((uintptr_t)x | (uintptr_t)s_cond | (uintptr_t)eps | (uintptr_t)z_t | (uintptr_t)packed) & 15) == 0,
                 "diffuse_pack: x, s_cond, eps, z_t and packed must be 16-byte aligned");
-    const int bpn = bpn_for(per / 4, n);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VDM_F32)
-        hipLaunchKernelGGL(diffuse_pack_kernel<float>, dim3(bpn * n), dim3(256), 0, s, x, s_cond, eps, seed, stream_id, seed_step, alpha, sigma, per,
-                           z_t, (float*)packed, bpn);
-    else
-        hipLaunchKernelGGL(diffuse_pack_kernel<bf16_t>, dim3(bpn * n), dim3(256), 0, s, x, s_cond, eps, seed, stream_id, seed_step, alpha, sigma, per,
-                           z_t, (bf16_t*)packed, bpn);
-    VDM_LAUNCH_CHECK("diffuse_pack_kernel");
-    return VDM_OK;
-}
-
-template <typename T>
-static void launch_pack_fields(int k, int blocks, int bpn, hipStream_t s, const float* z, const float* cond, int64_t per, void* out) {
-    if (k == 1) hipLaunchKernelGGL((pack_fields_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
-    else if (k == 2) hipLaunchKernelGGL((pack_fields_kernel<T, 2>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
-    else hipLaunchKernelGGL((pack_fields_kernel<T, 3>), dim3(blocks), dim3(256), 0, s, z, cond, per, (T*)out, bpn);
+    const DiffuseSrc src = {x, s_cond, eps, seed, stream_id, seed_step, alpha, sigma};
+    return launch_head(src, s_cond ? 1 : 0, n, per, dtype, z_t, packed, stream);        // (K = 0: +0 in channel 1)
 }
 
 extern "C" int vdm_pack_fields(const float* z, const float* cond, int k, int n, int64_t per, int dtype, void* out, void* stream) {
@@ -1432,27 +1418,8 @@ extern "C" int vdm_pack_fields(const float* z, const float* cond, int k, int n, 
     VDM_REQUIRE(per % 4 == 0, "pack_fields: per=%lld must be a multiple of 4", (long long)per);
     VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "pack_fields: bad dtype %d", dtype);
     VDM_REQUIRE((((uintptr_t)z | (uintptr_t)cond | (uintptr_t)out) & 15) == 0, "pack_fields: z, cond and out must be 16-byte aligned");
-    const int bpn = bpn_for(per / 4, n);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VDM_F32) launch_pack_fields<float>(k, bpn * n, bpn, s, z, cond, per, out);
-    else launch_pack_fields<bf16_t>(k, bpn * n, bpn, s, z, cond, per, out);
-    VDM_LAUNCH_CHECK("pack_fields_kernel");
-    return VDM_OK;
-}
-
-template <typename T>
-static void launch_diffuse_pack_fields(int k, int blocks, int bpn, hipStream_t s, const float* x, const float* cond, const float* eps,
-                                       uint64_t seed, uint64_t sid, const int32_t* seed_step, const float* alpha, const float* sigma,
-                                       int64_t per, float* z_t, void* packed) {
-    if (k == 1)
-        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 1>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
-                           z_t, (T*)packed, bpn);
-    else if (k == 2)
-        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 2>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
-                           z_t, (T*)packed, bpn);
-    else
-        hipLaunchKernelGGL((diffuse_pack_fields_kernel<T, 3>), dim3(blocks), dim3(256), 0, s, x, cond, eps, seed, sid, seed_step, alpha, sigma, per,
-                           z_t, (T*)packed, bpn);
+    const PlainSrc src = {z, cond};
+    return launch_head(src, k, n, per, dtype, nullptr, out, stream);
 }
 
 extern "C" int vdm_diffuse_pack_fields(const float* x, const float* cond, int k, const float* eps, uint64_t seed, uint64_t stream_id,
@@ -1466,12 +1433,8 @@ extern "C" int vdm_diffuse_pack_fields(const float* x, const float* cond, int k,
     VDM_REQUIRE((((uintptr_t)x | (uintptr_t)cond | (uintptr_t)eps | (uintptr_t)z_t | (uintptr_t)packed) & 15) == 0 &&
                     (((uintptr_t)alpha | (uintptr_t)sigma | (uintptr_t)seed_step) & 3) == 0,
                 "diffuse_pack_fields: x, cond, eps, z_t and packed must be 16-byte aligned, alpha / sigma / seed_step 4-byte aligned");
-    const int bpn = bpn_for(per / 4, n);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VDM_F32) launch_diffuse_pack_fields<float>(k, bpn * n, bpn, s, x, cond, eps, seed, stream_id, seed_step, alpha, sigma, per, z_t, packed);
-    else launch_diffuse_pack_fields<bf16_t>(k, bpn * n, bpn, s, x, cond, eps, seed, stream_id, seed_step, alpha, sigma, per, z_t, packed);
-    VDM_LAUNCH_CHECK("diffuse_pack_fields_kernel");
-    return VDM_OK;
+    const DiffuseSrc src = {x, cond, eps, seed, stream_id, seed_step, alpha, sigma};
+    return launch_head(src, k, n, per, dtype, z_t, packed, stream);
 }
 
 extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps, const float* eps_hat,
@@ -1502,16 +1465,8 @@ extern "C" int vdm_sfm_head(const float* x0, const float* x1, const float* eps, 
     VDM_REQUIRE((((uintptr_t)x0 | (uintptr_t)x1 | (uintptr_t)eps | (uintptr_t)x_t | (uintptr_t)packed) & 15) == 0 &&
                     (((uintptr_t)t | (uintptr_t)seed_step) & 3) == 0,
                 "sfm_head: x0, x1, eps, x_t and packed must be 16-byte aligned, t / seed_step 4-byte aligned");
-    const int bpn = bpn_for(per / 4, n);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == VDM_F32)
-        hipLaunchKernelGGL(sfm_head_kernel<float>, dim3(bpn * n), dim3(256), 0, s, x0, x1, eps, seed, stream_id, seed_step, t, sigma, cond, per, x_t,
-                           (float*)packed, bpn);
-    else
-        hipLaunchKernelGGL(sfm_head_kernel<bf16_t>, dim3(bpn * n), dim3(256), 0, s, x0, x1, eps, seed, stream_id, seed_step, t, sigma, cond, per,
-                           x_t, (bf16_t*)packed, bpn);
-    VDM_LAUNCH_CHECK("sfm_head_kernel");
-    return VDM_OK;
+    const FlowSrc src = {x0, x1, eps, seed, stream_id, seed_step, t, sigma, cond};
+    return launch_head(src, 1, n, per, dtype, x_t, packed, stream);
 }
 
 extern "C" int vdm_sfm_loss(const float* v_hat, const float* x0, const float* x1, const float* coef, int n, int64_t per, float* sums,

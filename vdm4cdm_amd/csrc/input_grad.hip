@@ -29,73 +29,9 @@ __device__ __forceinline__ int wrap_idx(int g, int n) {
     return r < 0 ? r + n : r;
 }
 
-template <typename T, int CIN>
-__global__ void __launch_bounds__(256) conv_in_dgrad_kernel(const T* __restrict__ dh, int C, int D, int H, int W, int circ,
-                                                            const float* __restrict__ wt, float* __restrict__ dz, float* __restrict__ ds,
-                                                            int tiles_x, int tiles_y, int tiles_z) {
-    __shared__ float4 img[IG_CK / 4][IG_HV];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tx = b % tiles_x;
-    b /= tiles_x;
-    const int ty = b % tiles_y;
-    b /= tiles_y;
-    const int tz = b % tiles_z;
-    const int n = b / tiles_z;
-    const int x0 = tx * IG_TX, y0 = ty * IG_TY, z0 = tz * IG_TZ;
-    const int lx = tid % IG_TX, ly = (tid / IG_TX) % IG_TY, lz = tid / (IG_TX * IG_TY);
-    const size_t nbase = (size_t)n * D * H * W;
-    float a0 = 0.f, a1 = 0.f;
-    for (int c0 = 0; c0 < C; c0 += IG_CK) {
-        __syncthreads();
-        for (int e = tid; e < IG_HV * (IG_CK / 4); e += 256) {
-            const int q = e % (IG_CK / 4), hv = e / (IG_CK / 4);
-            const int hx = hv % IG_HX, hy = (hv / IG_HX) % IG_HY, hz = hv / (IG_HX * IG_HY);
-            int gx = x0 - 1 + hx, gy = y0 - 1 + hy, gz = z0 - 1 + hz;
-            bool ok;
-            if (circ) {
-                gx = wrap_idx(gx, W); gy = wrap_idx(gy, H); gz = wrap_idx(gz, D);
-                ok = true;
-            } else {
-                ok = gx >= 0 && gx < W && gy >= 0 && gy < H && gz >= 0 && gz < D;
-            }
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok) v = ld_quad<T>(dh + (nbase + ((size_t)gz * H + gy) * W + gx) * C + c0 + 4 * q);
-            img[q][hv] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kz = 0; kz < 3; ++kz)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int hv = ((lz + 2 - kz) * IG_HY + (ly + 2 - ky)) * IG_HX + (lx + 2 - kx);
-                    const float* w = wt + ((size_t)((kz * 3 + ky) * 3 + kx) * C + c0) * CIN;
-#pragma unroll
-                    for (int q = 0; q < IG_CK / 4; ++q) {
-                        const float4 v = img[q][hv];
-                        const float* wq = w + 4 * q * CIN;
-                        a0 = fmaf(v.x, wq[0], a0); a0 = fmaf(v.y, wq[CIN], a0);
-                        a0 = fmaf(v.z, wq[2 * CIN], a0); a0 = fmaf(v.w, wq[3 * CIN], a0);
-                        if (CIN == 2) {
-                            a1 = fmaf(v.x, wq[1], a1); a1 = fmaf(v.y, wq[CIN + 1], a1);
-                            a1 = fmaf(v.z, wq[2 * CIN + 1], a1); a1 = fmaf(v.w, wq[3 * CIN + 1], a1);
-                        }
-                    }
-                }
-    }
-    const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-    if (x < W && y < H && z < D) {
-        const size_t o = nbase + ((size_t)z * H + y) * W + x;
-        dz[o] = a0;
-        if (CIN == 2 && ds) ds[o] = a1;
-    }
-}
-
-// K1t for up to three conditioning fields (ABI v18): conv_in has CIN = 1 + K <= 4 input channels.  The tiling, the LDS staging and the
-// summation order per output are those of conv_in_dgrad_kernel (taps, then channel quads, then the four channels of a quad: for
-// CIN <= 2 the bits are the same); NACC = 1 computes dz alone at the cost it has there, NACC = CIN also the K planes of ds [n][K][d][h][w].
+// K1t for conv_in's CIN = 1 + K <= 4 input channels (K conditioning fields, ABI v18).  Summation order per output: taps, then channel
+// quads, then the four channels of a quad.  NACC = 1 computes dz alone, NACC = CIN also the K planes of ds [n][K][d][h][w] (K = 1: the
+// [n][d][h][w] of vdm_conv_in_dgrad).  Both entries launch this kernel.
 template <typename T, int CIN, int NACC>
 __global__ void __launch_bounds__(256) conv_in_dgrad_fields_kernel(const T* __restrict__ dh, int C, int D, int H, int W, int circ,
                                                                    const float* __restrict__ wt, float* __restrict__ dz, float* __restrict__ ds,
@@ -166,34 +102,6 @@ __global__ void __launch_bounds__(256) conv_in_dgrad_fields_kernel(const T* __re
 
 using namespace vdm;
 
-extern "C" int vdm_conv_in_dgrad(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
-                                 float* dz, float* ds, void* stream) {
-    VDM_REQUIRE(dh && weight && dz, "conv_in_dgrad: NULL pointer (dh, weight and dz are required)");
-    VDM_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0, "conv_in_dgrad: bad grid n=%d d=%d h=%d w=%d", n, d, h, w);
-    VDM_REQUIRE(c == 16 || c == 32 || c == 48 || c == 64, "conv_in_dgrad: channels %d out of range (16, 32, 48 or 64)", c);
-    VDM_REQUIRE(cin == 1 || cin == 2, "conv_in_dgrad: input channels %d out of range (1 or 2)", cin);
-    VDM_REQUIRE(!ds || cin == 2, "conv_in_dgrad: ds needs cin == 2");
-    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "conv_in_dgrad: bad dtype %d", dtype);
-    VDM_REQUIRE(pad_mode == VDM_PAD_ZEROS || pad_mode == VDM_PAD_CIRCULAR, "conv_in_dgrad: bad pad_mode %d", pad_mode);
-    VDM_REQUIRE(((uintptr_t)dh & 15) == 0 && ((uintptr_t)weight & 3) == 0 && ((uintptr_t)dz & 3) == 0 && ((uintptr_t)ds & 3) == 0,
-                "conv_in_dgrad: dh must be 16-byte aligned, weight / dz / ds 4-byte aligned");
-    const int tx = (w + IG_TX - 1) / IG_TX, ty = (h + IG_TY - 1) / IG_TY, tz = (d + IG_TZ - 1) / IG_TZ;
-    const long long blocks = (long long)tx * ty * tz * n;
-    VDM_REQUIRE(blocks <= 0x7fffffffLL, "conv_in_dgrad: grid too large");
-    hipStream_t s = (hipStream_t)stream;
-    const int circ = pad_mode == VDM_PAD_CIRCULAR;
-    const dim3 grid((unsigned)blocks), blk(256);
-    if (dtype == VDM_F32) {
-        if (cin == 2) hipLaunchKernelGGL((conv_in_dgrad_kernel<float, 2>), grid, blk, 0, s, (const float*)dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
-        else hipLaunchKernelGGL((conv_in_dgrad_kernel<float, 1>), grid, blk, 0, s, (const float*)dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
-    } else {
-        if (cin == 2) hipLaunchKernelGGL((conv_in_dgrad_kernel<bf16_t, 2>), grid, blk, 0, s, (const bf16_t*)dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
-        else hipLaunchKernelGGL((conv_in_dgrad_kernel<bf16_t, 1>), grid, blk, 0, s, (const bf16_t*)dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
-    }
-    VDM_LAUNCH_CHECK("conv_in_dgrad_kernel");
-    return VDM_OK;
-}
-
 template <typename T, int CIN>
 static void launch_dgrad_fields(bool with_ds, dim3 grid, hipStream_t s, const void* dh, int c, int d, int h, int w, int circ, const float* weight,
                                 float* dz, float* ds, int tx, int ty, int tz) {
@@ -210,6 +118,29 @@ static void launch_dgrad_fields_cin(int cin, bool with_ds, dim3 grid, hipStream_
     else if (cin == 2) launch_dgrad_fields<T, 2>(with_ds, grid, s, dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
     else if (cin == 3) launch_dgrad_fields<T, 3>(with_ds, grid, s, dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
     else launch_dgrad_fields<T, 4>(with_ds, grid, s, dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
+}
+
+extern "C" int vdm_conv_in_dgrad(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,
+                                 float* dz, float* ds, void* stream) {
+    VDM_REQUIRE(dh && weight && dz, "conv_in_dgrad: NULL pointer (dh, weight and dz are required)");
+    VDM_REQUIRE(n > 0 && d > 0 && h > 0 && w > 0, "conv_in_dgrad: bad grid n=%d d=%d h=%d w=%d", n, d, h, w);
+    VDM_REQUIRE(c == 16 || c == 32 || c == 48 || c == 64, "conv_in_dgrad: channels %d out of range (16, 32, 48 or 64)", c);
+    VDM_REQUIRE(cin == 1 || cin == 2, "conv_in_dgrad: input channels %d out of range (1 or 2)", cin);
+    VDM_REQUIRE(!ds || cin == 2, "conv_in_dgrad: ds needs cin == 2");
+    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "conv_in_dgrad: bad dtype %d", dtype);
+    VDM_REQUIRE(pad_mode == VDM_PAD_ZEROS || pad_mode == VDM_PAD_CIRCULAR, "conv_in_dgrad: bad pad_mode %d", pad_mode);
+    VDM_REQUIRE(((uintptr_t)dh & 15) == 0 && ((uintptr_t)weight & 3) == 0 && ((uintptr_t)dz & 3) == 0 && ((uintptr_t)ds & 3) == 0,
+                "conv_in_dgrad: dh must be 16-byte aligned, weight / dz / ds 4-byte aligned");
+    const int tx = (w + IG_TX - 1) / IG_TX, ty = (h + IG_TY - 1) / IG_TY, tz = (d + IG_TZ - 1) / IG_TZ;
+    const long long blocks = (long long)tx * ty * tz * n;
+    VDM_REQUIRE(blocks <= 0x7fffffffLL, "conv_in_dgrad: grid too large");
+    hipStream_t s = (hipStream_t)stream;
+    const int circ = pad_mode == VDM_PAD_CIRCULAR;
+    const dim3 grid((unsigned)blocks);
+    if (dtype == VDM_F32) launch_dgrad_fields_cin<float>(cin, ds != nullptr, grid, s, dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
+    else launch_dgrad_fields_cin<bf16_t>(cin, ds != nullptr, grid, s, dh, c, d, h, w, circ, weight, dz, ds, tx, ty, tz);
+    VDM_LAUNCH_CHECK("conv_in_dgrad_fields_kernel");
+    return VDM_OK;
 }
 
 extern "C" int vdm_conv_in_dgrad_fields(const void* dh, int n, int d, int h, int w, int c, int dtype, int pad_mode, const float* weight, int cin,

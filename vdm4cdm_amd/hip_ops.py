@@ -744,20 +744,31 @@ def diffuse(x, eps, alpha, sigma, out=None):
     return out
 
 
+def _head_outputs(who, x, channels, dtype, want_z, z_out=None, packed_out=None):
+    """What the fused heads share: x [N, 1, D, H, W] (or [N, D, H, W]) fp32 -> (n, per, spatial shape, z fp32 or None, packed
+    [N, D, H, W, cpad(channels)] of `dtype`).  z_out / packed_out are validated and used instead of fresh tensors (z_out implies want_z).
+    The kernel owns 4 voxels per thread: a sample whose voxel count is no multiple of 4 is refused (ValueError)."""
+    n = x.shape[0]
+    per = x.numel() // n
+    if per % 4:
+        raise ValueError(f"{who}: {per} voxels per sample is not a multiple of 4")
+    assert x.dtype == torch.float32
+    sp = tuple(x.shape[2:]) if x.dim() == 5 else tuple(x.shape[1:])
+    packed = packed_out if packed_out is not None else torch.empty((n,) + sp + (cpad(channels, dtype),), dtype=dtype, device=x.device)
+    assert packed.dtype == dtype and packed.numel() == x.numel() * cpad(channels, dtype)
+    z = z_out if z_out is not None else (torch.empty_like(x) if want_z else None)
+    assert z is None or (z.dtype == torch.float32 and z.numel() == x.numel())
+    return n, per, sp, z, packed
+
+
 def diffuse_pack(x, s_cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False, z_out=None, packed_out=None):
     """Fused head of the training step (vdm_diffuse_pack): z_t = alpha[n] x + sigma[n] eps -> (z_t fp32 or None, conv_in's NDHWC input
     [N, D, H, W, cpad(2)] = {z_t, s_cond, 0...} in `dtype`).  eps None: drawn inside the kernel from Philox(seed, stream_id) - the field
     randn(out, seed, stream_id) would have written.  z_out / packed_out: write there instead of into fresh tensors (z_out implies want_z)."""
+    n, per, _, z, packed = _head_outputs("diffuse_pack", x, 2, dtype, want_z, z_out, packed_out)
     L = _lib.lib()
     _contig(x, s_cond, eps, alpha, sigma, z_out, packed_out)
-    n = x.shape[0]
-    per = x.numel() // n
-    assert x.dtype == torch.float32 and per % 4 == 0 and (s_cond is None or (s_cond.shape == x.shape and s_cond.dtype == torch.float32))
-    sp = tuple(x.shape[2:]) if x.dim() == 5 else tuple(x.shape[1:])
-    packed = packed_out if packed_out is not None else torch.empty((n,) + sp + (cpad(2, dtype),), dtype=dtype, device=x.device)
-    assert packed.dtype == dtype and packed.numel() == x.numel() * cpad(2, dtype)
-    z = z_out if z_out is not None else (torch.empty_like(x) if want_z else None)
-    assert z is None or (z.dtype == torch.float32 and z.numel() == x.numel())
+    assert s_cond is None or (s_cond.shape == x.shape and s_cond.dtype == torch.float32)
     check(L.vdm_diffuse_pack(_p(x), _p(s_cond), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per, dt_id(dtype),
                              _p(z), _p(packed), _s()), "vdm_diffuse_pack")
     return z, packed
@@ -767,49 +778,41 @@ def diffuse_pack_fields(x, cond, alpha, sigma, dtype, eps=None, seed=0, stream_i
     """diffuse_pack for K conditioning fields (vdm_diffuse_pack_fields): x [N, 1, D, H, W] (or [N, D, H, W]), cond [N, K, D, H, W], K in
     1..3 -> (z_t fp32 or None, packed [N, D, H, W, cpad(1 + K)] = {z_t, c_0 .. c_{K-1}, 0...}).  The noise is keyed as in diffuse_pack:
     z_t and channel 0 are the bits diffuse_pack gives for the same arguments."""
+    k = cond.shape[1]
+    n, per, sp, z, packed = _head_outputs("diffuse_pack_fields", x, 1 + k, dtype, want_z)
     L = _lib.lib()
     _contig(x, cond, eps, alpha, sigma)
-    n = x.shape[0]
-    per = x.numel() // n
-    sp = tuple(x.shape[2:]) if x.dim() == 5 else tuple(x.shape[1:])
-    assert x.dtype == cond.dtype == torch.float32 and cond.shape[0] == n and tuple(cond.shape[2:]) == sp
-    k = cond.shape[1]
-    if per % 4:
-        raise ValueError(f"diffuse_pack_fields: {per} voxels per sample is not a multiple of 4")
-    packed = torch.empty((n,) + sp + (cpad(1 + k, dtype),), dtype=dtype, device=x.device)
-    z = torch.empty_like(x) if want_z else None
+    assert cond.dtype == torch.float32 and cond.shape[0] == n and tuple(cond.shape[2:]) == sp
     check(L.vdm_diffuse_pack_fields(_p(x), _p(cond), k, _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per,
                                     dt_id(dtype), _p(z), _p(packed), _s()), "vdm_diffuse_pack_fields")
     return z, packed
 
 
-def conv_in_dgrad_fields(dh, weight, cin, circular, want_s):
-    """K1t for cin = 1 + K in 1..4 (vdm_conv_in_dgrad_fields): (dz [N, D, H, W], ds [N, K, D, H, W] or None) fp32 from dh (NDHWC
-    [N, D, H, W, C]) and conv_in's fp32 master weight [27, C, cin].  want_s False: dz alone (n_ds = 0)."""
+def _k1t(entry, dh, weight, cin, circular, ds_planes, tail=()):
+    """What the two K1t entries share: dh NDHWC [N, D, H, W, C], conv_in's fp32 master weight [27, C, cin] -> (dz [N, D, H, W], ds
+    [N, *ds_planes, D, H, W] or None when ds_planes is None), fp32.  tail: the entry's arguments between ds and the stream."""
     L = _lib.lib()
     _contig(dh, weight)
     n, d, h, w, c = dh.shape
     assert weight.dtype == torch.float32 and tuple(weight.shape) == (27, c, cin)
-    n_ds = cin - 1 if want_s else 0
     dz = torch.empty((n, d, h, w), dtype=torch.float32, device=dh.device)
-    ds = torch.empty((n, n_ds, d, h, w), dtype=torch.float32, device=dh.device) if n_ds else None
-    check(L.vdm_conv_in_dgrad_fields(_p(dh), n, d, h, w, c, dt_id(dh.dtype), _lib.PAD_CIRCULAR if circular else _lib.PAD_ZEROS, _p(weight),
-                                     cin, _p(dz), _p(ds), n_ds, _s()), "vdm_conv_in_dgrad_fields")
+    ds = torch.empty((n,) + ds_planes + (d, h, w), dtype=torch.float32, device=dh.device) if ds_planes is not None else None
+    check(getattr(L, entry)(_p(dh), n, d, h, w, c, dt_id(dh.dtype), _lib.PAD_CIRCULAR if circular else _lib.PAD_ZEROS, _p(weight), cin,
+                            _p(dz), _p(ds), *tail, _s()), entry)
     return dz, ds
+
+
+def conv_in_dgrad_fields(dh, weight, cin, circular, want_s):
+    """K1t for cin = 1 + K in 1..4 (vdm_conv_in_dgrad_fields): (dz [N, D, H, W], ds [N, K, D, H, W] or None) fp32 from dh (NDHWC
+    [N, D, H, W, C]) and conv_in's fp32 master weight [27, C, cin].  want_s False: dz alone (n_ds = 0)."""
+    n_ds = cin - 1 if want_s else 0
+    return _k1t("vdm_conv_in_dgrad_fields", dh, weight, cin, circular, (n_ds,) if n_ds else None, (n_ds,))
 
 
 def conv_in_dgrad(dh, weight, cin, circular, want_s):
     """K1t (vdm_conv_in_dgrad): the gradient of conv_in's input channels from dh = d loss / d conv_in output (NDHWC [N, D, H, W, C]).
     weight: conv_in's fp32 master weight [27, C, cin].  Returns (dz, ds or None), fp32 [N, D, H, W]."""
-    L = _lib.lib()
-    _contig(dh, weight)
-    n, d, h, w, c = dh.shape
-    assert weight.dtype == torch.float32 and tuple(weight.shape) == (27, c, cin)
-    dz = torch.empty((n, d, h, w), dtype=torch.float32, device=dh.device)
-    ds = torch.empty_like(dz) if want_s else None
-    check(L.vdm_conv_in_dgrad(_p(dh), n, d, h, w, c, dt_id(dh.dtype), _lib.PAD_CIRCULAR if circular else _lib.PAD_ZEROS, _p(weight), cin,
-                              _p(dz), _p(ds), _s()), "vdm_conv_in_dgrad")
-    return dz, ds
+    return _k1t("vdm_conv_in_dgrad", dh, weight, cin, circular, () if want_s else None)
 
 
 def schedule_grad_sums(dz, x, eps=None, seed=0, stream_id=0):
@@ -860,19 +863,11 @@ def sfm_head(x0, x1, t, sigma, dtype, cond=True, eps=None, seed=0, stream_id=0, 
     the kernel from Philox(seed, stream_id) - the field randn(out, seed, stream_id) would have written; sigma == 0: no noise is read or
     drawn.  x_out / packed_out: write there instead of into fresh tensors (x_out implies want_x).  The kernel owns 4 voxels per thread:
     a sample whose voxel count is no multiple of 4 is refused (ValueError)."""
-    n = x0.shape[0]
-    per = x0.numel() // n
-    if per % 4:
-        raise ValueError(f"sfm_head: {per} voxels per sample is not a multiple of 4")
+    n, per, _, x_t, packed = _head_outputs("sfm_head", x0, 2, dtype, want_x, x_out, packed_out)
     L = _lib.lib()
     _contig(x0, x1, t, eps, x_out, packed_out)
-    assert x0.dtype == x1.dtype == t.dtype == torch.float32 and x1.shape == x0.shape and t.numel() == n
+    assert x1.dtype == t.dtype == torch.float32 and x1.shape == x0.shape and t.numel() == n
     assert eps is None or (eps.dtype == torch.float32 and eps.shape == x0.shape)
-    sp = tuple(x0.shape[2:]) if x0.dim() == 5 else tuple(x0.shape[1:])
-    packed = packed_out if packed_out is not None else torch.empty((n,) + sp + (cpad(2, dtype),), dtype=dtype, device=x0.device)
-    assert packed.dtype == dtype and packed.numel() == x0.numel() * cpad(2, dtype)
-    x_t = x_out if x_out is not None else (torch.empty_like(x0) if want_x else None)
-    assert x_t is None or (x_t.dtype == torch.float32 and x_t.numel() == x0.numel())
     check(L.vdm_sfm_head(_p(x0), _p(x1), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(t), float(sigma), int(bool(cond)), n, per,
                          dt_id(dtype), _p(x_t), _p(packed), _s()), "vdm_sfm_head")
     return x_t, packed
