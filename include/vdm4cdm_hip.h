@@ -389,6 +389,25 @@ int vdm_sfm_head(const float* x0, const float* x1, const float* eps, uint64_t se
 int vdm_sfm_loss(const float* v_hat, const float* x0, const float* x1, const float* coef, int n, int64_t per, float* sums, float* d_v,
                  float* workspace, void* stream);
 
+/* ---- conditioning dropout of classifier-free guidance training (added under ABI v21) [VDM(p_uncond=, cfg_drop=): a random share of
+ * the training rows sees the null token (zeros) instead of its conditioning; w_cfg then guides the sampler] ---------------------------
+ * Every argument error (a required pointer NULL, rows <= 0, p outside [0, 1] or NaN, misalignment, k outside 1..3, and what
+ * vdm_diffuse_pack_fields refuses) returns VDM_ERR_ARG with a message before any launch.
+ *   vdm_cond_keep: keep[r] = 1.0f / 0.0f for r < rows, one uniform draw per GLOBAL row `row0 + r`: Philox4x32-10 with the key `seed`
+ *     mixed with *seed_step (NULL: the seed as it is) and the counter (row lo, row hi, 0xCFD0, 0); keep = unit(word 0) > p, the rule of
+ *     the fp32 dropout byte (p = 0 keeps every row, p = 1 none).  A row's draw does not depend on row0 / rows.
+ *   vdm_mask_rows: out[r][j] = keep[r] != 0 ? v[r][j] : +0.0f for r < rows, j < dim - a select: NaN / Inf of a dropped row do not
+ *     get through.  out == v is allowed.  float4 accesses when v and out are 16-byte aligned and dim % 4 == 0, scalar otherwise.
+ *   vdm_diffuse_pack_fields_keep: vdm_diffuse_pack_fields with a per-row keep of the conditioning planes, keep_s[n] (NULL: every row
+ *     kept - the launch of vdm_diffuse_pack_fields).  A dropped row (keep_s[n] == 0) gets +0 in planes 1 .. k of its pieces and its cond
+ *     planes are not read; z_t and channel 0 carry the bits of vdm_diffuse_pack_fields for the same arguments, with every row kept the
+ *     whole output does, and k = 1 gives the bits of vdm_diffuse_pack. */
+int vdm_cond_keep(float p, uint64_t seed, const int32_t* seed_step, uint64_t row0, int64_t rows, float* keep, void* stream);
+int vdm_mask_rows(const float* v, const float* keep, int64_t rows, int64_t dim, float* out, void* stream);
+int vdm_diffuse_pack_fields_keep(const float* x, const float* cond, int k, const float* eps, uint64_t seed, uint64_t stream_id,
+                                 const int32_t* seed_step, const float* alpha, const float* sigma, int n, int64_t per, int dtype,
+                                 float* z_t, void* packed, const float* keep_s, void* stream);
+
 /* ---- data path: crop + log-normalise + flip + permute on the device -----------------------------
  * Replaces the per-sample CPU DataLoader work of [REF src/dataset/CAMELS_3D_dataset.py:53-73] (AstroDataset.__getitem__) and
  * [REF src/dataset/augmentation.py:8-127] (Crop, LogTransform, Normalize, Flip, Permutate):

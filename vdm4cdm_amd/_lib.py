@@ -146,7 +146,10 @@ SIGNATURES = {
     "vdm_conv_in_dgrad_fields": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
     "vdm_sfm_head": (_i, [_p, _p, _p, _u64, _u64, _p, _p, _f, _i, _i, _i64, _i, _p, _p, _p]),
     "vdm_sfm_loss": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _p]),
-    "vdm_schedule_grad_sums": (_i, [_p, _p, _p, _u64, _u64, _p, _i, _i64, _p, _p, _p]),
+    "vdm_cond_keep": (_i, [_f, _u64, _p, _u64, _i64, _p, _p]),
+    "vdm_mask_rows": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "vdm_diffuse_pack_fields_keep": (_i, [_p, _p, _i, _p, _u64, _u64, _p, _p, _p, _i, _i64, _i, _p, _p, _p, _p]),
+    "vdm_schedule_grad_sums":(_i, [_p, _p, _p, _u64, _u64, _p, _i, _i64, _p, _p, _p]),
     "vdm_ancestral_step": (_i, [_p, _p, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_cfg": (_i, [_p, _p, _p, _f, _p, _p, _p, _u64, _i64, _p]),
     "vdm_ancestral_step_rows": (_i, [_p, _p, _p, _f, _p, _p, _p, _i, _i64, _p]),

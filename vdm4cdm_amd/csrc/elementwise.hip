@@ -605,11 +605,12 @@ __global__ void __launch_bounds__(256) randn_kernel(float* __restrict__ out, int
 
 // ---------------------------------------------------------------------------------------------
 // Head of the network: the NDHWC input of conv_in {z, c_0 .. c_{K-1}, 0 ...} in the compute dtype, written in the pass that makes z -
-// ONE 16-byte piece per voxel in both storage types (1 + K <= 4, K = 0 .. 3 conditioning planes).  One skeleton, head_kernel, and three
+// ONE 16-byte piece per voxel in both storage types (1 + K <= 4, K = 0 .. 3 conditioning planes).  One skeleton, head_kernel, and four
 // sources of what a thread owns (4 consecutive voxels: the four values zz of channel 0 and cc of the K planes):
 //   PlainSrc    vdm_pack_fields                            z and cond [n][K][per] as they are (ABI v18)
 //   DiffuseSrc  vdm_diffuse_pack, vdm_diffuse_pack_fields  z_t = alpha[n] x + sigma[n] eps, the bits of diffuse_kernel (ABI v11, v18)
 //   FlowSrc     vdm_sfm_head                               x_t = (1 - t[n]) x0 + t[n] x1 (+ sigma eps), the plane cond ? x0 : 0 (ABI v21)
+//   DiffuseKeepSrc  vdm_diffuse_pack_fields_keep           DiffuseSrc with a per-row keep of the K planes: +0 for a dropped row (ABI v21)
 // eps is drawn IN the kernel (Philox, the counters of randn_kernel: same (seed, stream id, element group) -> the same field vdm_randn
 // would have written) or read (supplied noise: parity tests).  z is also written as fp32 where it is asked for: randn + diffuse +
 // pack_input in one pass over x.  The 16-byte pieces of the packed tensor are re-dealt inside the wave so that every store instruction
@@ -739,6 +740,70 @@ struct DiffuseSrc {
         ld_planes<K>(cond, n4, ic, cc);
     }
 };
+
+// DiffuseSrc with a per-row keep of the conditioning planes (vdm_diffuse_pack_fields_keep: conditioning dropout of classifier-free
+// guidance training).  keep_s[n] is read once in seek; a block serves one sample, so the branch in load is uniform.  A dropped row
+// writes +0 into planes 1 .. K and never reads its cond planes; z_t / channel 0 are DiffuseSrc's.  keep_s NULL: every row kept.
+// A source type of its own: the instantiations of head_kernel<.., DiffuseSrc> behind the older entries are not touched.
+struct DiffuseKeepSrc {
+    static constexpr int KMIN = 1, KMAX = 3;
+    DiffuseSrc d;
+    const float* keep_s;
+    bool kept;                                                      // of the sample (seek)
+    template <int K>
+    __device__ __forceinline__ void seek(int n, int64_t per) {
+        d.template seek<K>(n, per);
+        kept = keep_s ? keep_s[n] != 0.f : true;
+    }
+    template <int K>
+    __device__ __forceinline__ void load(int64_t n4, int64_t ic, float (&zz)[4], float (&cc)[K > 0 ? K : 1][4]) const {
+        float nocond[1][4];
+        d.template load<0>(n4, ic, zz, nocond);
+        if (kept) {
+            ld_planes<K>(d.cond, n4, ic, cc);
+        } else {
+#pragma unroll
+            for (int f = 0; f < K; ++f)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) cc[f][j] = 0.f;
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Conditioning dropout of classifier-free guidance training (ABI v21): the per-row keep draw and the row select.
+//   cond_keep : keep[r] = unit(word 0 of Philox(key = mix_seed(seed, step), counter = (row lo, row hi, 0xCFD0, 0))) > p ? 1 : 0 with
+//               row = row0 + r the GLOBAL row (rank * B + i) - the rule of the fp32 dropout byte: p = 0 keeps all, p = 1 drops all
+//   mask_rows : out[r][j] = keep[r] != 0 ? v[r][j] : +0 - a select, not a product: NaN / Inf of a dropped row do not get through
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) cond_keep_kernel(float p, uint64_t seed0, const int32_t* __restrict__ seed_step, uint64_t row0,
+                                                       int64_t rows, float* __restrict__ keep) {
+    const uint64_t seed = mix_seed(seed0, seed_step);
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < rows; r += (int64_t)gridDim.x * 256) {
+        const uint64_t row = row0 + (uint64_t)r;
+        uint32_t rnd[4];
+        Philox::gen((uint32_t)row, (uint32_t)(row >> 32), 0xCFD0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+        keep[r] = u32_to_unit(rnd[0]) > p ? 1.f : 0.f;
+    }
+}
+
+// grid (x blocks, row blocks): a block works on one row at a time, so the select is uniform (a dropped row is never read).  vec: both
+// pointers 16-byte aligned and dim % 4 == 0.  out may be v (no __restrict__ on the two): every element is read and written by one thread.
+__global__ void __launch_bounds__(256) mask_rows_kernel(const float* v, const float* __restrict__ keep, int64_t rows, int64_t dim, int vec,
+                                                       float* out) {
+    for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+        const bool kept = keep[r] != 0.f;
+        const float* vr = v + (size_t)r * dim;
+        float* o = out + (size_t)r * dim;
+        if (vec) {
+            const int64_t d4 = dim >> 2;
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < d4; i += (int64_t)gridDim.x * 256)
+                reinterpret_cast<float4*>(o)[i] = kept ? reinterpret_cast<const float4*>(vr)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < dim; i += (int64_t)gridDim.x * 256) o[i] = kept ? vr[i] : 0.f;
+        }
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Flow matching (ABI v21): the head and the loss of an SFM training step.  Their arithmetic is pinned, bit for bit, to the chain of
@@ -1435,6 +1500,47 @@ extern "C" int vdm_diffuse_pack_fields(const float* x, const float* cond, int k,
                 "diffuse_pack_fields: x, cond, eps, z_t and packed must be 16-byte aligned, alpha / sigma / seed_step 4-byte aligned");
     const DiffuseSrc src = {x, cond, eps, seed, stream_id, seed_step, alpha, sigma};
     return launch_head(src, k, n, per, dtype, z_t, packed, stream);
+}
+
+extern "C" int vdm_diffuse_pack_fields_keep(const float* x, const float* cond, int k, const float* eps, uint64_t seed, uint64_t stream_id,
+                                            const int32_t* seed_step, const float* alpha, const float* sigma, int n, int64_t per,
+                                            int dtype, float* z_t, void* packed, const float* keep_s, void* stream) {
+    VDM_REQUIRE(x && cond && alpha && sigma && packed,
+                "diffuse_pack_fields_keep: NULL pointer (x, cond, alpha, sigma and packed are required)");
+    VDM_REQUIRE(k >= 1 && k <= 3, "diffuse_pack_fields_keep: %d conditioning fields out of range (1 to 3)", k);
+    VDM_REQUIRE(n > 0 && per > 0, "diffuse_pack_fields_keep: bad sizes n=%d per=%lld", n, (long long)per);
+    VDM_REQUIRE(per % 4 == 0, "diffuse_pack_fields_keep: per=%lld must be a multiple of 4", (long long)per);
+    VDM_REQUIRE(dtype == VDM_F32 || dtype == VDM_BF16, "diffuse_pack_fields_keep: bad dtype %d", dtype);
+    VDM_REQUIRE((((uintptr_t)x | (uintptr_t)cond | (uintptr_t)eps | (uintptr_t)z_t | (uintptr_t)packed) & 15) == 0 &&
+                    (((uintptr_t)alpha | (uintptr_t)sigma | (uintptr_t)seed_step | (uintptr_t)keep_s) & 3) == 0,
+                "diffuse_pack_fields_keep: x, cond, eps, z_t and packed must be 16-byte aligned, alpha / sigma / seed_step / keep_s 4-byte "
+                "aligned");
+    const DiffuseSrc src = {x, cond, eps, seed, stream_id, seed_step, alpha, sigma};
+    if (!keep_s) return launch_head(src, k, n, per, dtype, z_t, packed, stream);      // every row kept: vdm_diffuse_pack_fields' kernel
+    const DiffuseKeepSrc ksrc = {src, keep_s};
+    return launch_head(ksrc, k, n, per, dtype, z_t, packed, stream);
+}
+
+extern "C" int vdm_cond_keep(float p, uint64_t seed, const int32_t* seed_step, uint64_t row0, int64_t rows, float* keep, void* stream) {
+    VDM_REQUIRE(keep, "cond_keep: keep is NULL");
+    VDM_REQUIRE(rows > 0, "cond_keep: rows = %lld (must be positive)", (long long)rows);
+    VDM_REQUIRE(p >= 0.f && p <= 1.f, "cond_keep: p = %g outside [0, 1]", (double)p);               // (refuses NaN too)
+    VDM_REQUIRE((((uintptr_t)keep | (uintptr_t)seed_step) & 3) == 0, "cond_keep: keep / seed_step must be 4-byte aligned");
+    hipLaunchKernelGGL(cond_keep_kernel, dim3(grid_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, p, seed, seed_step, row0, rows, keep);
+    VDM_LAUNCH_CHECK("cond_keep_kernel");
+    return VDM_OK;
+}
+
+extern "C" int vdm_mask_rows(const float* v, const float* keep, int64_t rows, int64_t dim, float* out, void* stream) {
+    VDM_REQUIRE(v && keep && out, "mask_rows: NULL pointer (v, keep and out are required)");
+    VDM_REQUIRE(rows > 0 && dim > 0, "mask_rows: bad sizes rows=%lld dim=%lld", (long long)rows, (long long)dim);
+    VDM_REQUIRE((((uintptr_t)v | (uintptr_t)keep | (uintptr_t)out) & 3) == 0, "mask_rows: v, keep and out must be 4-byte aligned");
+    const int vec = (((uintptr_t)v | (uintptr_t)out) & 15) == 0 && dim % 4 == 0;
+    int64_t gy = rows < 65535 ? rows : 65535, cap = (2048 + gy - 1) / gy, bx = ((vec ? dim / 4 : dim) + 255) / 256;
+    if (bx > cap) bx = cap;
+    hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)bx, (unsigned)gy), dim3(256), 0, (hipStream_t)stream, v, keep, rows, dim, vec, out);
+    VDM_LAUNCH_CHECK("mask_rows_kernel");
+    return VDM_OK;
 }
 
 extern "C" int vdm_loss_terms_rng(const float* x, const float* eps, uint64_t seed_eps, uint64_t stream_eps, const float* eps_hat,

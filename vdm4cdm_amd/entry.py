@@ -13,7 +13,9 @@
 Environment knobs (build-side, all optional): VDM4CDM_MAX_STEPS, VDM4CDM_PRECISION (bf16|fp32), VDM4CDM_SAMPLING_STEPS,
 VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing config), VDM4CDM_SAMPLE_BATCH (chains per sampler
 call and rank in generate_3D*; default 1), VDM4CDM_SAMPLER (ancestral | ddim | dpm2m: the sampler of generate_3D*), VDM4CDM_RESUME (a checkpoint of the same run to continue from, or "last": the newest one
-in the run directory).
+in the run directory), VDM4CDM_P_UNCOND / VDM4CDM_CFG_DROP (VDM training scripts: conditioning dropout for classifier-free guidance - the
+share of rows that sees the null token, default 0, and what is dropped, v | s | vs, default v; generate_3D* read VDM4CDM_W_CFG and
+VDM4CDM_CFG_DROP through utils.get_model).
 Multi-GPU: launch the same script under ``python -m torch.distributed.run --nproc-per-node N`` (one rank per GPU, RCCL).
 """
 import argparse
@@ -41,6 +43,18 @@ def _seed_everything(seed=42):
     torch.manual_seed(seed)
     from .vdm_model import reset_train_generators
     reset_train_generators()                 # the training step's own generators restart from the new seed
+
+
+def _cfg_dropout_kwargs():
+    """VDM4CDM_P_UNCOND (default 0) / VDM4CDM_CFG_DROP (default v) of the VDM training scripts -> LightVDM's p_uncond= / cfg_drop=.
+    Read and validated before data, model or GPU work."""
+    from .vdm_model import check_cfg_args
+    try:
+        p, drop = check_cfg_args(os.environ.get("VDM4CDM_P_UNCOND") or "0", os.environ.get("VDM4CDM_CFG_DROP") or "v",
+                                 who="VDM4CDM_P_UNCOND / VDM4CDM_CFG_DROP")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return {"p_uncond": p, "cfg_drop": drop}
 
 
 def _resume_path(log_dir, experiment_name):
@@ -136,7 +150,7 @@ def train_vdm3d(variant, argv=None):
     channel_names, n_cond = parse_fields(field_in, field_out)
     dataset_name, chs, n_values, val_every, name_pat, thick = VDM3D_VARIANTS[variant]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
-    resume = _resume_path(log_dir, name)
+    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
     _seed_everything(42)
     batch_size = 2
     dm = data.get_dataset(dataset_name=dataset_name, suite_name="Astrid", return_func=data.cond_return_func(n_cond, bool(n_values)),
@@ -148,7 +162,7 @@ def train_vdm3d(variant, argv=None):
         dropout_prob=0.1, conv_padding_mode="circular" if cropsize == 256 else "zeros", n_attention_heads=4,
         backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
     vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, n_values > 0, x_channel=n_cond), gamma_max=13.3,
-                             learning_rate=3.0e-4)
+                             learning_rate=3.0e-4, **cfg_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=val_every,
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
                       default_root_dir=log_dir, experiment_name=name,
@@ -183,7 +197,7 @@ def train3d_c_c(variant, argv=None):
     cropsize, name_pat, thick = TRAIN3D_VARIANTS[variant]
     c = TRAIN3D_COMMON
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"), name_pat.format(i=field_in, o=field_out)
-    resume = _resume_path(log_dir, name)
+    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
     _seed_everything(42)
 
     dm = data.get_dataset(dataset_name=c["dataset_name"], suite_name=c["suite_name"], return_func=data.cond_return_func(n_cond),
@@ -194,7 +208,8 @@ def train3d_c_c(variant, argv=None):
         t_conditioning=True, norm_groups=c["norm_groups"], mid_attn=False, dropout_prob=c["dropout_prob"],
         conv_padding_mode=c["conv_padding_mode"], n_attention_heads=4, backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
     vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=_figure_closure(dm, thick, True, x_channel=n_cond), gamma_min=c["gamma_min"],
-                             gamma_max=c["gamma_max"], noise_schedule=c["noise_schedule"], learning_rate=c["learning_rate"])
+                             gamma_max=c["gamma_max"], noise_schedule=c["noise_schedule"], learning_rate=c["learning_rate"],
+                             **cfg_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=c["val_check_interval"],
                       gradient_clip_val=c["gradient_clip_val"], every_n_train_steps=c["every_n_train_steps"],
                       default_root_dir=log_dir, experiment_name=name,
@@ -497,7 +512,7 @@ def train_uc_c(argv=None):
         raise SystemExit("usage: train_uc_c_from_field_name.py <field_name>")
     field_name = argv[0]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"), f"LH_uc_c_{field_name}"
-    resume = _resume_path(log_dir, name)
+    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -508,7 +523,7 @@ def train_uc_c(argv=None):
                                  v_conditioning_dims=[6], t_conditioning=True, norm_groups=8, dropout_prob=0.1,
                                  conv_padding_mode="circular", n_attention_heads=4, backend="torch")
     vdm = vdm_model.LightVDM(score_model=score_model, gamma_min=-13.3, gamma_max=13.3, noise_schedule="learned_linear",
-                             draw_figure=None)
+                             draw_figure=None, **cfg_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=5000, gradient_clip_val=0.5,
                       every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
     trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)

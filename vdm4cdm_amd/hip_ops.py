@@ -761,28 +761,69 @@ def _head_outputs(who, x, channels, dtype, want_z, z_out=None, packed_out=None):
     return n, per, sp, z, packed
 
 
-def diffuse_pack(x, s_cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False, z_out=None, packed_out=None):
+def _check_keep(who, keep, n):
+    assert keep.dtype == torch.float32 and keep.numel() == n and keep.is_contiguous(), f"{who}: keep must be {n} contiguous fp32 values"
+
+
+def cond_keep(p, seed, rows, device, row0=0, out=None):
+    """The per-row keep of conditioning dropout (vdm_cond_keep): [rows] fp32 {0, 1}, row r kept iff the uniform draw of GLOBAL row
+    row0 + r - Philox keyed by `seed` (mixed with SEED_STEP inside the kernel when a captured step set it) - exceeds p."""
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=device)
+    _check_keep("cond_keep", out, rows)
+    check(_lib.lib().vdm_cond_keep(float(p), int(seed), _p(SEED_STEP), int(row0), rows, _p(out), _s()), "vdm_cond_keep")
+    return out
+
+
+def mask_rows(v, keep, out=None):
+    """vdm_mask_rows: out[r] = v[r] where keep[r] != 0, +0 elsewhere (a select: NaN / Inf of a dropped row do not get through).
+    v: fp32 [rows, ...]; out may be v."""
+    _contig(v, out)
+    assert v.dtype == torch.float32
+    rows = v.shape[0]
+    _check_keep("mask_rows", keep, rows)
+    if out is None:
+        out = torch.empty_like(v)
+    assert out.dtype == torch.float32 and out.shape == v.shape
+    check(_lib.lib().vdm_mask_rows(_p(v), _p(keep), rows, v.numel() // rows, _p(out), _s()), "vdm_mask_rows")
+    return out
+
+
+def diffuse_pack(x, s_cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False, z_out=None, packed_out=None, keep_s=None):
     """Fused head of the training step (vdm_diffuse_pack): z_t = alpha[n] x + sigma[n] eps -> (z_t fp32 or None, conv_in's NDHWC input
     [N, D, H, W, cpad(2)] = {z_t, s_cond, 0...} in `dtype`).  eps None: drawn inside the kernel from Philox(seed, stream_id) - the field
-    randn(out, seed, stream_id) would have written.  z_out / packed_out: write there instead of into fresh tensors (z_out implies want_z)."""
+    randn(out, seed, stream_id) would have written.  z_out / packed_out: write there instead of into fresh tensors (z_out implies want_z).
+    keep_s ([N] fp32, needs s_cond): rows with keep_s == 0 get +0 instead of s_cond, which is not read there
+    (vdm_diffuse_pack_fields_keep with k = 1: the same bits)."""
     n, per, _, z, packed = _head_outputs("diffuse_pack", x, 2, dtype, want_z, z_out, packed_out)
     L = _lib.lib()
     _contig(x, s_cond, eps, alpha, sigma, z_out, packed_out)
     assert s_cond is None or (s_cond.shape == x.shape and s_cond.dtype == torch.float32)
+    if keep_s is not None and s_cond is not None:
+        _check_keep("diffuse_pack", keep_s, n)
+        check(L.vdm_diffuse_pack_fields_keep(_p(x), _p(s_cond), 1, _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n,
+                                             per, dt_id(dtype), _p(z), _p(packed), _p(keep_s), _s()), "vdm_diffuse_pack_fields_keep")
+        return z, packed
     check(L.vdm_diffuse_pack(_p(x), _p(s_cond), _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per, dt_id(dtype),
                              _p(z), _p(packed), _s()), "vdm_diffuse_pack")
     return z, packed
 
 
-def diffuse_pack_fields(x, cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False):
+def diffuse_pack_fields(x, cond, alpha, sigma, dtype, eps=None, seed=0, stream_id=0, want_z=False, keep_s=None):
     """diffuse_pack for K conditioning fields (vdm_diffuse_pack_fields): x [N, 1, D, H, W] (or [N, D, H, W]), cond [N, K, D, H, W], K in
     1..3 -> (z_t fp32 or None, packed [N, D, H, W, cpad(1 + K)] = {z_t, c_0 .. c_{K-1}, 0...}).  The noise is keyed as in diffuse_pack:
-    z_t and channel 0 are the bits diffuse_pack gives for the same arguments."""
+    z_t and channel 0 are the bits diffuse_pack gives for the same arguments.  keep_s ([N] fp32): rows with keep_s == 0 get +0 in all
+    K planes and their cond is not read (vdm_diffuse_pack_fields_keep)."""
     k = cond.shape[1]
     n, per, sp, z, packed = _head_outputs("diffuse_pack_fields", x, 1 + k, dtype, want_z)
     L = _lib.lib()
     _contig(x, cond, eps, alpha, sigma)
     assert cond.dtype == torch.float32 and cond.shape[0] == n and tuple(cond.shape[2:]) == sp
+    if keep_s is not None:
+        _check_keep("diffuse_pack_fields", keep_s, n)
+        check(L.vdm_diffuse_pack_fields_keep(_p(x), _p(cond), k, _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n,
+                                             per, dt_id(dtype), _p(z), _p(packed), _p(keep_s), _s()), "vdm_diffuse_pack_fields_keep")
+        return z, packed
     check(L.vdm_diffuse_pack_fields(_p(x), _p(cond), k, _p(eps), int(seed), int(stream_id), _p(SEED_STEP), _p(alpha), _p(sigma), n, per,
                                     dt_id(dtype), _p(z), _p(packed), _s()), "vdm_diffuse_pack_fields")
     return z, packed

@@ -114,7 +114,9 @@ class NetStep:
     the rows at a device-side index, copy of z into both halves of the batch-doubled buffer under w_cfg (guided + v-masked rows of one
     forward, VDM._cfg_pair), UNet forward].  s_cond: one conditioning cube serves every row.  R: rows the UNet sees, W: table width."""
 
-    def __init__(self, net, t_norm, z, s_cond, v_conditionings, w_cfg=None, mask_fn=None):
+    def __init__(self, net, t_norm, z, s_cond, v_conditionings, w_cfg=None, mask_fn=None, cfg_drop="v"):
+        """cfg_drop (under w_cfg): what the unguided half of the rows masks - "v": the vector conditionings (mask_fn), "s": the conditioning
+        cube (zero planes, concatenated once here like s_cond itself), "vs": both."""
         from . import hip_ops as ops
         dev, B, cfg = net.flat.device, z.shape[0], w_cfg is not None
         self.net, self.B, self.W, self.R = net, B, net.table_width, 2 * B if cfg else B
@@ -125,12 +127,12 @@ class NetStep:
                 self.table_t = ops.CondTable(net.cond_specs(t_norm, None, fl, which="t"), t_norm.shape[0], self.W).forward(save=False)
             vs = [v.to(device=dev, dtype=torch.float32).expand(B, -1).contiguous() for v in v_conditionings]
             if cfg:
-                vs = [torch.cat([v, m], dim=0).contiguous() for v, m in zip(vs, mask_fn(vs))]
+                vs = [torch.cat([v, m], dim=0).contiguous() for v, m in zip(vs, mask_fn(vs) if "v" in cfg_drop else vs)]
             if vs:
                 self.table_v = ops.CondTable(net.cond_specs(None, vs, fl, which="v"), self.R, self.W).forward(save=False)
         if s_cond is not None:
             s_cond = s_cond.to(dev).expand(B, *s_cond.shape[1:])
-            s_cond = (torch.cat([s_cond, s_cond], dim=0) if cfg else s_cond).contiguous()
+            s_cond = (torch.cat([s_cond, torch.zeros_like(s_cond) if "s" in cfg_drop else s_cond], dim=0) if cfg else s_cond).contiguous()
         self.s_cond = s_cond
         self.table = torch.zeros(self.R, self.W, device=dev)
         self.zz = torch.empty(self.R, *z.shape[1:], device=z.device) if cfg else None
@@ -195,7 +197,8 @@ class StepLoop:
         return self.result if self.out is None else self.out
 
 
-def hip_graph_sampler(net, z, coef, noise, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None, return_all=False):
+def hip_graph_sampler(net, z, coef, noise, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None, return_all=False,
+                      cfg_drop="v"):
     """The multi-step sampling loop on the HIP backend, shared by the VDM ancestral sampler and the SFM Euler integrator: per step
     [NetStep, fused update z <- ratio * (z - cs * net_out) + scale * noise (the w_cfg blend inside it: the guided estimate is never
     materialised), step counter + 1]; coef[n][4] = {ratio, cs, scale, network time} is read on the device at the row of the device-side
@@ -205,7 +208,7 @@ def hip_graph_sampler(net, z, coef, noise, verbose, use_graph, s_cond, v_conditi
     step = torch.zeros(1, dtype=torch.int32, device=z.device)
     seeds_dev, seed = (noise.seeds_dev, None) if noise.seeds is not None else (None, noise.batch_seed)
     noise_buf = noise.feed and noise.feed.buf
-    net_step = NetStep(net, coef[:, 3].contiguous(), z, s_cond, v_conditionings, w_cfg, mask_fn)
+    net_step = NetStep(net, coef[:, 3].contiguous(), z, s_cond, v_conditionings, w_cfg, mask_fn, cfg_drop)
 
     def one_step():
         eps_hat, eps_uncond = net_step(z, step)
@@ -236,7 +239,8 @@ class _NoStepNoise:
         pass
 
 
-def hip_multistep_sampler(net, z, coef, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None, return_all=False):
+def hip_multistep_sampler(net, z, coef, verbose, use_graph, s_cond, v_conditionings, w_cfg=None, mask_fn=None, return_all=False,
+                          cfg_drop="v"):
     """The deterministic multistep loop on the HIP backend (VDM: DDIM / DPM-Solver++(2M) on the data prediction, SFM: Euler /
     Adams-Bashforth 2 on the velocity): per step [NetStep, K9m: est = e_z z + e_e net_out (the w_cfg blend inside it), z <- w_z z +
     w_x est + w_p prev, prev <- est, step counter + 1]; coef[n][8] = {e_z, e_e, w_z, w_x, w_p, network time, 0, 0} is read on the device
@@ -247,7 +251,7 @@ def hip_multistep_sampler(net, z, coef, verbose, use_graph, s_cond, v_conditioni
     # prev is never initialised: row 0 has w_p = 0 and K9m does not read prev there.  StepLoop's warm-up replay runs step 0 and leaves
     # its estimate in prev - harmless for the same reason (only z and the counter are put back).
     prev = torch.empty_like(z)
-    net_step = NetStep(net, coef[:, 5].contiguous(), z, s_cond, v_conditionings, w_cfg, mask_fn)
+    net_step = NetStep(net, coef[:, 5].contiguous(), z, s_cond, v_conditionings, w_cfg, mask_fn, cfg_drop)
 
     def one_step():
         eps_hat, eps_uncond = net_step(z, step)
@@ -364,10 +368,11 @@ def hip_ddnm_sampler(model, z, y, A, AT, operator, n, sch, noise, use_graph, ret
     noise_buf = noise.feed and noise.feed.buf
     tables = ops.DdnmTables(coef, sched, noise.seeds_dev, batch_stream=noise.batch_stream)
     cfg = model.w_cfg is not None and not model.training
-    assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+    if cfg:
+        model._cfg_check(kwargs)
     w_cfg = float(model.w_cfg) if cfg else 0.0
     net_step = NetStep(model.score_model, coef[:, 5].contiguous(), z, kwargs.get("s_conditioning"),
-                       list(kwargs.get("v_conditionings") or []), w_cfg if cfg else None, model.cfg_mask)
+                       list(kwargs.get("v_conditionings") or []), w_cfg if cfg else None, model.cfg_mask, model.cfg_drop)
     x_r = torch.empty_like(z)
     kind = getattr(operator, "kind", None)
     y = y.to(torch.float32)

@@ -137,6 +137,15 @@ def batch_shapes(batch):
     return {k: one(v) for k, v in batch.items()}
 
 
+def cfg_dropout_record(model):
+    """{"p_uncond", "cfg_drop"} of a LightVDM-like module (None: the model has no conditioning dropout, e.g. flow matching) - written
+    into every checkpoint next to the trainer state; a resumed fit must match it and utils.get_model reads cfg_drop from it."""
+    inner = getattr(model, "model", None)
+    if inner is None or not hasattr(inner, "p_uncond"):
+        return None
+    return {"p_uncond": float(inner.p_uncond), "cfg_drop": str(inner.cfg_drop)}
+
+
 def read_checkpoint(path, mmap=False):
     """A checkpoint file on the host (tensors on the CPU; mmap: mapped, so that reading `global_step` does not read the weights)."""
     return torch.load(path, map_location="cpu", mmap=bool(mmap), weights_only=True)
@@ -299,6 +308,8 @@ class Trainer:
         os.makedirs(d, exist_ok=True)
         path = os.path.join(d, f"epoch={epoch}-step={self.global_step}.ckpt")
         payload = {"state_dict": model.state_dict(), "global_step": self.global_step, "epoch": epoch}
+        if cfg_dropout_record(model) is not None:
+            payload["cfg_dropout"] = cfg_dropout_record(model)
         if state is not None:
             payload["trainer_state"] = state
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -342,6 +353,12 @@ class Trainer:
         """ckpt_path: a checkpoint written by fit - the run continues at its global_step, inside the same epoch at the batch after the
         last one consumed, bit for bit as if it had never stopped (same world size, batch size and data module)."""
         resume = None if ckpt_path is None else self._read_resume(ckpt_path, datamodule)
+        if resume is not None:                                # conditioning dropout is part of the run, like its batch size
+            saved, mine = resume[0].get("cfg_dropout") or {"p_uncond": 0.0, "cfg_drop": "v"}, cfg_dropout_record(model)
+            if mine is not None and (float(saved["p_uncond"]) != mine["p_uncond"]
+                                     or (mine["p_uncond"] > 0 and saved["cfg_drop"] != mine["cfg_drop"])):
+                raise ValueError(f"{os.fspath(ckpt_path)} was written by a run with p_uncond={saved['p_uncond']} cfg_drop={saved['cfg_drop']!r}, "
+                                 f"this model has p_uncond={mine['p_uncond']} cfg_drop={mine['cfg_drop']!r}: a resumed run must keep them")
         dev = self.device
         if dev is None:
             dev = "cuda" if torch.cuda.is_available() else "cpu"

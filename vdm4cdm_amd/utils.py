@@ -108,6 +108,7 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
             return None                                      # as in the reference (generate_3D.py refuses SFM)
         raise ValueError(f"Unknown model type {config['type']}")
     from . import networks, vdm_model
+    w_cfg, cfg_drop = guidance_knobs(config)             # (bad values: a ValueError before any model or GPU work)
     n_values = config.get("conditioning_values", 6)
     cropsize = config.get("cropsize", 128)
     score_model = networks.CUNet(
@@ -118,14 +119,46 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
         t_conditioning=True, norm_groups=8, mid_attn=False, dropout_prob=0.1,
         conv_padding_mode="circular" if cropsize == 256 else "zeros", n_attention_heads=4,
         backend=backend, precision=precision or config.get("precision", "bf16"))
-    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=None, gamma_max=13.3, learning_rate=3.0e-4)
     path = config.get("ckpt_path")
-    if load_ckpt and path:
-        if os.path.exists(path):
-            vdm.load_state_dict(torch.load(path, map_location="cpu")["state_dict"])
-        else:
-            print(f"[vdm4cdm_amd] checkpoint {path} not found: using seeded random weights (no trained weights ship with this repo)")
+    ck = torch.load(path, map_location="cpu") if (load_ckpt and path and os.path.exists(path)) else None
+    recorded = ck.get("cfg_dropout") if isinstance(ck, dict) else None
+    if w_cfg is not None:
+        if cfg_drop is None:                               # by default what the checkpoint's training run dropped
+            cfg_drop = recorded["cfg_drop"] if recorded else "v"
+        vdm_model.check_cfg_args(0.0, cfg_drop, score_model, "get_model(w_cfg)")
+        if not recorded or float(recorded["p_uncond"]) == 0.0:
+            print(f"[vdm4cdm_amd] WARNING: w_cfg={w_cfg} asks for classifier-free guidance, but "
+                  + ("the checkpoint records p_uncond=0" if recorded else "no checkpoint records conditioning dropout (p_uncond)")
+                  + f": the network never saw the null token, its unguided branch (cfg_drop={cfg_drop!r}) is untrained", flush=True)
+    vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=None, gamma_max=13.3, learning_rate=3.0e-4,
+                             **({} if w_cfg is None else {"w_cfg": w_cfg, "cfg_drop": cfg_drop}))
+    if ck is not None:
+        vdm.load_state_dict(ck["state_dict"])
+    elif load_ckpt and path:
+        print(f"[vdm4cdm_amd] checkpoint {path} not found: using seeded random weights (no trained weights ship with this repo)")
     return vdm
+
+
+def guidance_knobs(config):
+    """(w_cfg or None, cfg_drop or None) of a generation run: $VDM4CDM_W_CFG / config["w_cfg"] and $VDM4CDM_CFG_DROP /
+    config["cfg_drop"] (the environment wins).  Host-only; a value that is no finite number / none of "v", "s", "vs" is a ValueError."""
+    import math
+    import os
+    from .vdm_model import CFG_DROPS
+    w = os.environ.get("VDM4CDM_W_CFG")
+    w = config.get("w_cfg") if w in (None, "") else w
+    if w is not None:
+        try:
+            w = float(w)
+        except (TypeError, ValueError):
+            raise ValueError(f"w_cfg={w!r} is not a number (VDM4CDM_W_CFG / config key w_cfg)") from None
+        if not math.isfinite(w):
+            raise ValueError(f"w_cfg={w!r} must be finite (VDM4CDM_W_CFG / config key w_cfg)")
+    drop = os.environ.get("VDM4CDM_CFG_DROP")
+    drop = config.get("cfg_drop") if drop in (None, "") else drop
+    if drop is not None and drop not in CFG_DROPS:
+        raise ValueError(f"cfg_drop={drop!r} (VDM4CDM_CFG_DROP / config key cfg_drop): one of {', '.join(map(repr, CFG_DROPS))}")
+    return w, drop
 
 
 class MaskOperator:

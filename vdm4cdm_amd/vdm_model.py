@@ -85,11 +85,12 @@ class _LearnedDiffuseFn(torch.autograd.Function):
     or regenerated from the same counters); alpha / sigma are [B] tensors of torch autograd over (gamma_b, gamma_w)."""
 
     @staticmethod
-    def forward(ctx, alpha, sigma, x, eps, rng, s_cond, dtype):
+    def forward(ctx, alpha, sigma, x, eps, rng, s_cond, dtype, keep_s=None):
         from . import hip_ops as ops
         head = ops.diffuse_pack_fields if (s_cond is not None and s_cond.shape[1] > 1) else ops.diffuse_pack      # [B, K, ...], K = 2, 3
+        kw = {} if keep_s is None else {"keep_s": keep_s}          # conditioning dropout: the dropped rows' planes are +0 (p_uncond)
         z_t, xin = head(x, s_cond, alpha.detach().contiguous(), sigma.detach().contiguous(), dtype, eps=eps, seed=rng[0],
-                        stream_id=rng[1], want_z=True)
+                        stream_id=rng[1], want_z=True, **kw)
         ctx.save_for_backward(x, eps)
         ctx.rng = rng
         ctx.mark_non_differentiable(xin)
@@ -100,9 +101,9 @@ class _LearnedDiffuseFn(torch.autograd.Function):
         from . import hip_ops as ops
         x, eps = ctx.saved_tensors
         if dz is None:
-            return (None,) * 7
+            return (None,) * 8
         sums = ops.schedule_grad_sums(dz.contiguous(), x, eps, *ctx.rng)
-        return sums[:, 0], sums[:, 1], None, None, None, None, None
+        return sums[:, 0], sums[:, 1], None, None, None, None, None, None
 
 
 class _LearnedElboFn(torch.autograd.Function):
@@ -127,11 +128,85 @@ class _LearnedElboFn(torch.autograd.Function):
         return g * d, 0.5 * g * sums[:, 0], None, None, None, None
 
 
+CFG_DROPS = ("v", "s", "vs")
+COND_KEEP_SEED_SALT = 0xCFD05EED          # cond_keep_seed = torch.initial_seed() ^ this: a stream of its own, not train_generator's
+_GOLDEN64, _MASK64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
+
+
+class CfgConditioningError(ValueError, AssertionError):
+    """Guidance asked to mask a conditioning that was not passed (a ValueError; also an AssertionError, which this case raised before)."""
+
+
+def check_cfg_args(p_uncond=0.0, cfg_drop="v", score_model=None, who="VDM"):
+    """Validates (p_uncond, cfg_drop) on the host; with a network also that it has the conditionings cfg_drop names.  Returns
+    (float p_uncond, cfg_drop)."""
+    try:
+        p = float(p_uncond)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: p_uncond={p_uncond!r} is not a number") from None
+    if not (math.isfinite(p) and 0.0 <= p <= 1.0):
+        raise ValueError(f"{who}: p_uncond={p_uncond!r} must be a finite number in [0, 1]")
+    if cfg_drop not in CFG_DROPS:
+        raise ValueError(f"{who}: cfg_drop={cfg_drop!r} (one of {', '.join(map(repr, CFG_DROPS))})")
+    if score_model is not None:
+        if "v" in cfg_drop and not getattr(score_model, "v_conditioning_dims", None):
+            raise ValueError(f"{who}: cfg_drop={cfg_drop!r} drops the vector conditionings, but the network has no v_conditioning_dims")
+        if "s" in cfg_drop and not getattr(score_model, "s_conditioning_channels", 0):
+            raise ValueError(f"{who}: cfg_drop={cfg_drop!r} drops the conditioning fields, but the network has s_conditioning_channels=0")
+    return p, cfg_drop
+
+
+def _rows(keep, t):
+    return keep.view((-1,) + (1,) * (t.dim() - 1))
+
+
+class _MaskRowsFn(torch.autograd.Function):
+    """vdm_mask_rows with its gradient: rows with keep == 0 are +0 in the output and in the gradient (a select in both directions)."""
+
+    @staticmethod
+    def forward(ctx, v, keep):
+        from . import hip_ops as ops
+        ctx.save_for_backward(keep)
+        return ops.mask_rows(v.contiguous(), keep)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import hip_ops as ops
+        g = g.contiguous()
+        return ops.mask_rows(g, ctx.saved_tensors[0], out=g), None
+
+
+class _MaskGradFn(torch.autograd.Function):
+    """Identity whose gradient is row-masked: for a conditioning field the fused head has already dropped (its forward never reads the
+    dropped rows), so that the ds planes K1t returns are +0 in those rows."""
+
+    @staticmethod
+    def forward(ctx, s, keep):
+        ctx.save_for_backward(keep)
+        return s.view_as(s)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import hip_ops as ops
+        g = g.contiguous()
+        return ops.mask_rows(g, ctx.saved_tensors[0], out=g), None
+
+
 class VDM(nn.Module):
     def __init__(self, score_model, noise_schedule="fixed_linear", gamma_min=-13.3, gamma_max=13.3,
-                 antithetic_time_sampling=True, data_noise=DATA_NOISE, w_cfg=None):
+                 antithetic_time_sampling=True, data_noise=DATA_NOISE, w_cfg=None, p_uncond=0.0, cfg_drop="v"):
+        """p_uncond / cfg_drop: classifier-free guidance training - in training mode every global row sees, with probability p_uncond
+        and on its own, the null token (zeros) instead of the conditioning(s) cfg_drop names ("v": the vector conditionings, "s": the
+        conditioning fields, all K planes, "vs": both, the same rows).  With w_cfg the unguided half of the sampler's batch-doubled
+        forward masks the same conditioning(s).  p_uncond == 0: the training step is exactly the one without the feature."""
         super().__init__()
         assert noise_schedule in ("fixed_linear", "learned_linear")
+        self.p_uncond, self.cfg_drop = check_cfg_args(p_uncond, cfg_drop)
+        if self.p_uncond > 0 or w_cfg is not None:     # (the feature is in use: the network must have what cfg_drop names)
+            check_cfg_args(p_uncond, cfg_drop, score_model)
+        self.last_cond_keep = None               # [B] fp32 {0, 1} of the latest training step that drew one (a graph replay refreshes it)
+        self._cond_keep_seed = None
+        self._cond_keep_calls = 0                # eager steps: mixed into the seed on the host (a captured step: hip_ops.SEED_STEP)
         self.score_model = score_model
         self.noise_schedule = noise_schedule
         self.gamma_min = float(gamma_min)
@@ -181,18 +256,80 @@ class VDM(nn.Module):
         the masking value is not in the reference tree - [INFERRED] zeros, the usual null token of a vector conditioning)."""
         return [torch.zeros_like(v) for v in v_conditionings]
 
+    def _cfg_check(self, kwargs):
+        """(mask v?, mask s?) of the unguided half under w_cfg; raises before any GPU work when what cfg_drop names was not passed."""
+        drop_v, drop_s = "v" in self.cfg_drop, "s" in self.cfg_drop
+        check_cfg_args(self.p_uncond, self.cfg_drop, self.score_model, "w_cfg")
+        if drop_v and kwargs.get("v_conditionings") is None:
+            raise CfgConditioningError(f"Need v_conditionings to mask out (w_cfg with cfg_drop={self.cfg_drop!r})")
+        if drop_s and kwargs.get("s_conditioning") is None:
+            raise CfgConditioningError(f"Need s_conditioning to mask out (w_cfg with cfg_drop={self.cfg_drop!r})")
+        return drop_v, drop_s
+
+    # ---------------------------------------------------------------- conditioning dropout (classifier-free guidance training)
+    @property
+    def cond_keep_seed(self):
+        """Philox seed of the keep stream: derived once per model from torch.initial_seed() and a constant - nothing is drawn from
+        train_generator, so the times, noise fields and dropout masks of a run do not depend on p_uncond."""
+        if self._cond_keep_seed is None:
+            self._cond_keep_seed = (torch.initial_seed() ^ COND_KEEP_SEED_SALT) & 0x7fffffffffffffff
+        return self._cond_keep_seed
+
+    def _draw_keep(self, B, device, hip):
+        """The [B] fp32 keep of this training step (None: eval mode or p_uncond == 0 - nothing is drawn or launched).  Row i of rank r is
+        global row r B + i.  HIP: one vdm_cond_keep launch, Philox counters (row, 0xCFD0), key = cond_keep_seed mixed with the step - the
+        device counter of a captured step, else this model's host call counter.  Torch backend: torch.rand(B) > p from the rank's
+        noise generator (not the Philox rows)."""
+        if not (self.training and self.p_uncond > 0.0):
+            return None
+        rank, _ = self._rank_world()
+        if hip:
+            from . import hip_ops as ops
+            seed = self.cond_keep_seed
+            if ops.SEED_STEP is None:
+                seed = (seed + (self._cond_keep_calls & 0xFFFFFFFF) * _GOLDEN64) & _MASK64
+                self._cond_keep_calls += 1
+            keep = ops.cond_keep(self.p_uncond, seed, B, device, row0=rank * B)
+        else:
+            keep = (torch.rand(B, device=device, generator=self._rank_noise_gen(device, rank)) > self.p_uncond).to(torch.float32)
+        self.last_cond_keep = keep
+        return keep
+
+    def _drop_conditioning(self, kwargs, keep, x, hip, head_drops_s=False):
+        """kwargs with the conditionings cfg_drop names replaced by their row-masked copies (null token: zeros).  head_drops_s: the fused
+        head writes the dropped rows' planes itself (keep_s) and the network never reads s_conditioning - only its gradient is masked."""
+        kw, B = dict(kwargs), x.shape[0]
+        if "v" in self.cfg_drop and kw.get("v_conditionings"):
+            vs = []
+            for v in kw["v_conditionings"]:
+                v = v.to(device=x.device, dtype=torch.float32)
+                v = v.expand(B, *v.shape[1:]) if v.shape[0] != B else v
+                vs.append(_MaskRowsFn.apply(v, keep) if hip else torch.where(_rows(keep, v) != 0, v, torch.zeros_like(v)))
+            kw["v_conditionings"] = vs
+        if "s" in self.cfg_drop and kw.get("s_conditioning") is not None:
+            s = kw["s_conditioning"].to(device=x.device, dtype=torch.float32)
+            s = s.expand(B, *s.shape[1:]) if s.shape[0] != B else s
+            if not hip:
+                kw["s_conditioning"] = torch.where(_rows(keep, s) != 0, s, torch.zeros_like(s))
+            elif not head_drops_s:
+                kw["s_conditioning"] = _MaskRowsFn.apply(s, keep)
+            elif s.requires_grad:
+                kw["s_conditioning"] = _MaskGradFn.apply(s, keep)
+        return kw
+
     def _cfg_pair(self, zt, t, kwargs):
         """Classifier-free guidance (notebook frame vdm_model.py:318-327): conditional and v-masked noise estimates from ONE
         batch-doubled UNet forward (rows 0..B-1 with the given v_conditionings, rows B..2B-1 with them masked)."""
-        assert "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+        drop_v, drop_s = self._cfg_check(kwargs)
         B = zt.shape[0]
-        vs = [v.to(zt.device).expand(B, *v.shape[1:]) if v.shape[0] != B else v.to(zt.device) for v in kwargs["v_conditionings"]]
         kw = dict(kwargs)
-        kw["v_conditionings"] = [torch.cat([v, m], dim=0) for v, m in zip(vs, self.cfg_mask(vs))]
+        if kwargs.get("v_conditionings") is not None:
+            vs = [v.to(zt.device).expand(B, *v.shape[1:]) if v.shape[0] != B else v.to(zt.device) for v in kwargs["v_conditionings"]]
+            kw["v_conditionings"] = [torch.cat([v, m], dim=0) for v, m in zip(vs, self.cfg_mask(vs) if drop_v else vs)]
         if kw.get("s_conditioning") is not None:
             sc = kw["s_conditioning"]
             sc = sc.expand(B, *sc.shape[1:]) if sc.shape[0] != B else sc
-            kw["s_conditioning"] = torch.cat([sc, sc], dim=0)
+            kw["s_conditioning"] = torch.cat([sc, torch.zeros_like(sc) if drop_s else sc], dim=0)      # (cfg_drop "s": the zero cube)
         t2 = torch.cat([t.expand(B), t.expand(B)]) if torch.is_tensor(t) else t
         eps = self.score_model(torch.cat([zt, zt], dim=0), t=t2, **kw)
         return eps[:B], eps[B:]
@@ -223,8 +360,9 @@ class VDM(nn.Module):
         bpd = 1.0 / (numel * math.log(2.0))
         x = x.to(torch.float32).contiguous()
         hip = self._hip(x)
+        keep = self._draw_keep(B, x.device, hip)      # conditioning dropout: None unless training with p_uncond > 0
         if hip and self.noise_schedule == "learned_linear":
-            return self._hip_learned_loss(x, times, eps, eps0, numel, bpd, kwargs)
+            return self._hip_learned_loss(x, times, eps, eps0, numel, bpd, kwargs, keep)
         if not hip:
             if times is None:
                 times = self.sample_times(B, x.device)
@@ -272,15 +410,21 @@ class VDM(nn.Module):
                 s_c = kwargs.get("s_conditioning") if sm.s_conditioning_channels else None
                 assert s_c is not None or not sm.s_conditioning_channels, "s_conditioning_channels=1 needs s_conditioning"
                 dt = torch.bfloat16 if sm.precision == "bf16" else torch.float32
+                # conditioning dropout of the fields: the head writes +0 for the dropped rows (keep_s); none: today's launches
+                hk = {"keep_s": keep} if (keep is not None and "s" in self.cfg_drop and s_c is not None) else {}
                 if sm.s_conditioning_channels > 1:         # K = 2, 3 conditioning fields: the same head with K planes
                     s_c = _cond_fields(s_c, x, sm.s_conditioning_channels)
-                    z_t, xin = ops.diffuse_pack_fields(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True)
+                    z_t, xin = ops.diffuse_pack_fields(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True, **hk)
                 else:
                     if s_c is not None:
                         s_c = s_c.to(device=x.device, dtype=torch.float32).expand(x.shape).contiguous()
-                    z_t, xin = ops.diffuse_pack(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True)
+                    z_t, xin = ops.diffuse_pack(x, s_c, sc[1], sc[2], dt, seed=rng[0][0], stream_id=rng[0][1], want_z=True, **hk)
+                if keep is not None:
+                    kwargs = self._drop_conditioning(kwargs, keep, x, True, head_drops_s=True)
                 eps_hat = self.score_model(z_t, t=sc[4], _packed_input=xin, **kwargs)
             else:
+                if keep is not None:
+                    kwargs = self._drop_conditioning(kwargs, keep, x, True)
                 z_t = ops.diffuse(x, eps.contiguous(), sc[1], sc[2])
                 if self.w_cfg is None or self.training:    # get_pred_noise's plain branch, t_norm straight from the scalar kernel
                     eps_hat = self.score_model(z_t, t=sc[4], **kwargs)
@@ -300,6 +444,8 @@ class VDM(nn.Module):
                 eps = torch.randn(x.shape, device=x.device, generator=g) if eps is None else eps
                 eps0 = torch.randn(x.shape, device=x.device, generator=g) if eps0 is None else eps0
             z_t = self.alpha(g_t).view(bc) * x + self.sigma(g_t).view(bc) * eps
+            if keep is not None:
+                kwargs = self._drop_conditioning(kwargs, keep, x, False)
             eps_hat = self.get_pred_noise(z_t, g_t, **kwargs)
             diff = (0.5 * self.dgamma_dt(times) * ((eps - eps_hat) ** 2).sum(red)).mean() * bpd
             sum_x2 = (x ** 2).sum(red)
@@ -312,7 +458,7 @@ class VDM(nn.Module):
                    "reconstruction_loss": recons.detach()}
         return loss, metrics
 
-    def _hip_learned_loss(self, x, times, eps, eps0, numel, bpd, kwargs):
+    def _hip_learned_loss(self, x, times, eps, eps0, numel, bpd, kwargs, keep=None):
         """get_loss of noise_schedule="learned_linear" on the HIP backend.  The activation-sized work is the fixed-linear path's kernels
         (fused head K7, K8) plus the network's input gradients (K1t dz, K6i dL/dt_norm) and K7b; the [B]-sized scalar side - gamma_t,
         alpha_t, sigma_t, t_norm, the diffusion weight |w| and the latent / reconstruction terms - is torch autograd over (gamma_b,
@@ -339,7 +485,11 @@ class VDM(nn.Module):
         elif s_c is not None:
             s_c = s_c.to(device=dev, dtype=torch.float32).expand(x.shape).contiguous()
         dt = torch.bfloat16 if sm.precision == "bf16" else torch.float32
-        z_t, xin = _LearnedDiffuseFn.apply(self.alpha(g_t), self.sigma(g_t), x, None if eps is None else eps.contiguous(), rng_e, s_c, dt)
+        keep_s = keep if (keep is not None and "s" in self.cfg_drop and s_c is not None) else None      # (None: today's launches)
+        z_t, xin = _LearnedDiffuseFn.apply(self.alpha(g_t), self.sigma(g_t), x, None if eps is None else eps.contiguous(), rng_e, s_c, dt,
+                                           *(() if keep_s is None else (keep_s,)))
+        if keep is not None:
+            kwargs = self._drop_conditioning(kwargs, keep, x, True, head_drops_s=True)
         if self.w_cfg is None or self.training:
             eps_hat = sm(z_t, t=t_norm, _packed_input=xin, **kwargs)
         else:
@@ -460,10 +610,11 @@ class VDM(nn.Module):
         coef = self.multistep_table(n_sampling_steps, order, lower_order_final)
         if self._hip(z):
             cfg = self.w_cfg is not None and not self.training
-            assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+            if cfg:
+                self._cfg_check(kwargs)
             return hip_multistep_sampler(self.score_model, z, coef.to(device=z.device, dtype=torch.float32).contiguous(), verbose,
                                          use_graph, kwargs.get("s_conditioning"), list(kwargs.get("v_conditionings") or []),
-                                         w_cfg=float(self.w_cfg) if cfg else None, mask_fn=self.cfg_mask, return_all=return_all)
+                                         w_cfg=float(self.w_cfg) if cfg else None, mask_fn=self.cfg_mask, return_all=return_all, cfg_drop=self.cfg_drop)
         steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1, device=z.device)
         return multistep_loop(coef, z, lambda i, zt: self.get_pred_noise(zt=zt, gamma_t=self.gamma(steps[i]), **kwargs), return_all)
 
@@ -490,10 +641,11 @@ class VDM(nn.Module):
         if self._hip(z):                                   # (return_all: the same captured step, z copied out after every replay)
             coef = self.step_table(n_sampling_steps).to(device=z.device, dtype=torch.float32).contiguous()
             cfg = self.w_cfg is not None and not self.training
-            assert not cfg or "v_conditionings" in kwargs, "Need v_conditionings to mask out"
+            if cfg:
+                self._cfg_check(kwargs)
             return hip_graph_sampler(self.score_model, z, coef, noise, verbose, use_graph, kwargs.get("s_conditioning"),
                                      list(kwargs.get("v_conditionings") or []), w_cfg=float(self.w_cfg) if cfg else None,
-                                     mask_fn=self.cfg_mask, return_all=return_all)
+                                     mask_fn=self.cfg_mask, return_all=return_all, cfg_drop=self.cfg_drop)
         steps = torch.linspace(1.0, 0.0, n_sampling_steps + 1, device=device)
         zs = []
         rng = range(n_sampling_steps)
@@ -647,11 +799,14 @@ class LightVDM(nn.Module):
         """The random stream this module owns besides the shared training generators: the torch backend's per-rank noise generator
         (VDM._rank_noise_gen), for checkpoints."""
         g = getattr(self.model, "_noise_gen", None)
+        st = {"cond_keep_calls": int(self.model._cond_keep_calls)} if self.model._cond_keep_calls else {}      # (eager conditioning dropout)
         if g is None:
-            return {}
-        return {"noise_gen": g.get_state(), "noise_gen_device": str(g.device), "noise_gen_key": [int(k) for k in self.model._noise_gen_key]}
+            return st
+        return {**st, "noise_gen": g.get_state(), "noise_gen_device": str(g.device),
+                "noise_gen_key": [int(k) for k in self.model._noise_gen_key]}
 
     def load_rng_state_dict(self, state):
+        self.model._cond_keep_calls = int(state.get("cond_keep_calls", 0))
         self.model._noise_gen = None
         if state.get("noise_gen") is not None:
             g = torch.Generator(device=state["noise_gen_device"])
