@@ -578,6 +578,20 @@ int vdm_ddnm_advance(int32_t* cursor, const int32_t* sched, int n_sched, int32_t
 /* out[0] += sum x^2 (caller zeroes).  workspace: >= 2048 floats (fixed-order fold: bit-reproducible). */
 int vdm_sumsq(const float* x, int64_t n, float* out, float* workspace, void* stream);
 
+/* ---- exponential moving average of the weights (added under ABI v21: two new entries, nothing existing changes, so the version stays;
+ * csrc/ema.hip) [LightVDM / LightSFM(ema_decay=): the averaged weights a trained model is sampled from] ------
+ * ema[i] <- ema[i] + w * (p[i] - ema[i]) over n fp32 elements, w = 1 - d_k, d_k = warmup ? min(decay, (1 + k) / (10 + k)) : decay with
+ * k = *num_updates read on the DEVICE (NULL: k = 0).  Every operation is rounded on its own, in this order and never fused:
+ *   q = rn((float)(1 + k) / (float)(10 + k)) ; d = min(decay, q) ; w = rn(1 - d) ; e' = rn(e + rn(w * rn(p - e)))
+ * so a float32 reference that rounds operation by operation gives the same bits.  The counter is NOT bumped: one step may update several
+ * tensors with the same k, the caller enqueues vdm_step_inc after the last one.  Both pointers 16-byte aligned: float4 accesses and a
+ * scalar tail; otherwise (4-byte aligned) scalar accesses - the schedule scalars go through here with n = 1.  ema or p NULL, n < 0,
+ * decay not a finite number in [0, 1), ema == p: VDM_ERR_ARG, nothing is launched.  n == 0: VDM_OK, nothing is launched. */
+int vdm_ema_update(float* ema, const float* p, int64_t n, float decay, int warmup, const int32_t* num_updates, void* stream);
+/* a[i] <-> b[i] over n fp32 elements, in place and without a temporary (evaluation under the averaged weights: every pointer a captured
+ * graph holds stays valid).  Alignment as above.  NULL pointers, n < 0, overlapping ranges (a == b included): VDM_ERR_ARG. */
+int vdm_swap(float* a, float* b, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

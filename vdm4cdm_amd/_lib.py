@@ -166,6 +166,8 @@ SIGNATURES = {
     "vdm_train_scalars": (_i, [_p, _p, _i, _i, _i, _f, _f, _f, _p, _u64, _p, _p]),
     "vdm_elbo_assemble": (_i, [_p, _p, _i, _f, _f, _f, _f, _p, _p]),
     "vdm_clip_scale": (_i, [_p, _i64, _p, _f, _p]),
+    "vdm_ema_update": (_i, [_p, _p, _i64, _f, _i, _p, _p]),
+    "vdm_swap": (_i, [_p, _p, _i64, _p]),
 }
 
 

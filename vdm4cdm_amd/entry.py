@@ -15,7 +15,9 @@ VDM4CDM_LOG_DIR, VDM4CDM_CROPSIZE_2D / VDM4CDM_BATCH_2D (shrink the 2D plumbing 
 call and rank in generate_3D*; default 1), VDM4CDM_SAMPLER (ancestral | ddim | dpm2m: the sampler of generate_3D*), VDM4CDM_RESUME (a checkpoint of the same run to continue from, or "last": the newest one
 in the run directory), VDM4CDM_P_UNCOND / VDM4CDM_CFG_DROP (VDM training scripts: conditioning dropout for classifier-free guidance - the
 share of rows that sees the null token, default 0, and what is dropped, v | s | vs, default v; generate_3D* read VDM4CDM_W_CFG and
-VDM4CDM_CFG_DROP through utils.get_model).
+VDM4CDM_CFG_DROP through utils.get_model), VDM4CDM_EMA_DECAY (training scripts: keep an exponential moving average of the weights with
+this decay, e.g. 0.9999; unset: none) and VDM4CDM_WEIGHTS (generate_3D*: ema | raw - which weights of the checkpoint to sample from;
+default: the averaged ones when the checkpoint holds them).
 Multi-GPU: launch the same script under ``python -m torch.distributed.run --nproc-per-node N`` (one rank per GPU, RCCL).
 """
 import argparse
@@ -55,6 +57,20 @@ def _cfg_dropout_kwargs():
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return {"p_uncond": p, "cfg_drop": drop}
+
+
+def _ema_kwargs():
+    """VDM4CDM_EMA_DECAY of the training scripts (e.g. 0.9999) -> the Light module's ema_decay=; unset or empty: no EMA.  Read and
+    validated before data, model or GPU work."""
+    from .ema import check_ema_args
+    raw = os.environ.get("VDM4CDM_EMA_DECAY")
+    if raw is None or not raw.strip():
+        return {}
+    try:
+        decay, _ = check_ema_args(raw.strip(), True, "VDM4CDM_EMA_DECAY")
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    return {"ema_decay": decay}
 
 
 def _resume_path(log_dir, experiment_name):
@@ -150,7 +166,7 @@ def train_vdm3d(variant, argv=None):
     channel_names, n_cond = parse_fields(field_in, field_out)
     dataset_name, chs, n_values, val_every, name_pat, thick = VDM3D_VARIANTS[variant]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
-    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
+    resume, cfg_kw = _resume_path(log_dir, name), {**_cfg_dropout_kwargs(), **_ema_kwargs()}
     _seed_everything(42)
     batch_size = 2
     dm = data.get_dataset(dataset_name=dataset_name, suite_name="Astrid", return_func=data.cond_return_func(n_cond, bool(n_values)),
@@ -197,7 +213,7 @@ def train3d_c_c(variant, argv=None):
     cropsize, name_pat, thick = TRAIN3D_VARIANTS[variant]
     c = TRAIN3D_COMMON
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-3D-2024"), name_pat.format(i=field_in, o=field_out)
-    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
+    resume, cfg_kw = _resume_path(log_dir, name), {**_cfg_dropout_kwargs(), **_ema_kwargs()}
     _seed_everything(42)
 
     dm = data.get_dataset(dataset_name=c["dataset_name"], suite_name=c["suite_name"], return_func=data.cond_return_func(n_cond),
@@ -254,7 +270,7 @@ def train_sfm3d(variant, argv=None):
     parse_fields(field_in, field_out, multi=False)
     dataset_name, chs, n_values, batch_size, name_pat, thick = SFM3D_VARIANTS[variant]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-3D"), name_pat.format(i=field_in, o=field_out, c=cropsize)
-    resume = _resume_path(log_dir, name)
+    resume, ema_kw = _resume_path(log_dir, name), _ema_kwargs()
     _seed_everything(42)
 
     def return_func(fields, params):
@@ -268,7 +284,8 @@ def train_sfm3d(variant, argv=None):
         v_conditioning_dims=[] if n_values == 0 else [n_values], t_conditioning=True, norm_groups=8, mid_attn=False,
         dropout_prob=0.1, conv_padding_mode="circular" if cropsize == 256 else "zeros", n_attention_heads=4,
         backend="hip", precision=os.environ.get("VDM4CDM_PRECISION", "bf16"))
-    sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=_sfm_figure_closure(dm, thick, n_values > 0), learning_rate=3.0e-4)
+    sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=_sfm_figure_closure(dm, thick, n_values > 0), learning_rate=3.0e-4,
+                             **ema_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=1000,
                       gradient_clip_val=0.5, every_n_train_steps=10_000,
                       default_root_dir=log_dir, experiment_name=name,
@@ -289,7 +306,7 @@ def train_sfm_c_uc_2d(argv=None):
     field_in, field_out = argv
     parse_fields(field_in, field_out, multi=False)
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/sfm4cdm-2D"), f"LH_c_uc_{field_in}_to_{field_out}"
-    resume = _resume_path(log_dir, name)
+    resume, ema_kw = _resume_path(log_dir, name), _ema_kwargs()
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -298,7 +315,7 @@ def train_sfm_c_uc_2d(argv=None):
     velocity_model = networks.CUNet(shape=(1, cropsize, cropsize), chs=[48, 96, 192, 384], s_conditioning_channels=1,
                                     v_conditioning_dims=[], t_conditioning=True, norm_groups=8, mid_attn=True, dropout_prob=0.1,
                                     conv_padding_mode="circular", n_attention_heads=4, backend="torch")
-    sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=None)
+    sfm = sfm_model.LightSFM(velocity_model=velocity_model, draw_figure=None, **ema_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=1000, gradient_clip_val=0.5,
                       every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
     trainer.fit(model=sfm, datamodule=dm, ckpt_path=resume)
@@ -314,7 +331,7 @@ def train_uc_uc(argv=None):
         raise SystemExit("usage: train_uc_uc_from_field_name.py <field_name>")
     field_name = argv[0]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"), f"LH_uc_uc_{field_name}"
-    resume = _resume_path(log_dir, name)
+    resume, ema_kw = _resume_path(log_dir, name), _ema_kwargs()
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))
@@ -325,7 +342,7 @@ def train_uc_uc(argv=None):
                                  v_conditioning_dims=[], t_conditioning=True, norm_groups=8, dropout_prob=0.1,
                                  conv_padding_mode="circular", n_attention_heads=4, backend="torch")
     vdm = vdm_model.LightVDM(score_model=score_model, gamma_min=-13.3, gamma_max=13.3, noise_schedule="learned_linear",
-                             draw_figure=None)
+                             draw_figure=None, **ema_kw)
     trainer = Trainer(max_steps=int(os.environ.get("VDM4CDM_MAX_STEPS", 1_000_000)), val_check_interval=5000, gradient_clip_val=0.5,
                       every_n_train_steps=10_000, default_root_dir=log_dir, experiment_name=name, device="cpu")
     trainer.fit(model=vdm, datamodule=dm, ckpt_path=resume)
@@ -381,6 +398,15 @@ def _sampler_name():
     if raw not in ("ancestral", "ddim", "dpm2m"):
         raise SystemExit(f"VDM4CDM_SAMPLER={raw!r}: must be one of ancestral, ddim, dpm2m")
     return raw
+
+
+def _weights_name():
+    """VDM4CDM_WEIGHTS: ema | raw - the checkpoint's weights the generate scripts sample from (utils.get_model; unset: the averaged
+    ones when the checkpoint holds them).  Checked here before any model or GPU work, so that a bad value fails at once."""
+    raw = os.environ.get("VDM4CDM_WEIGHTS")
+    if raw not in (None, "", "ema", "raw"):
+        raise SystemExit(f"VDM4CDM_WEIGHTS={raw!r}: must be ema or raw")
+    return raw or None
 
 
 def _sample_repetitions(model, config, batch, device, rep, first_chain, rank, world, n_steps, per_call=1, sampler="ancestral"):
@@ -447,6 +473,7 @@ def generate_3d(argv=None, configs_path=None):
     assert args.runtype in ["CV_12_12", "CV_1_128"]
     per_call = _sample_batch()
     sampler = _sampler_name()
+    _weights_name()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "CV")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -484,6 +511,7 @@ def generate_3d_1p(argv=None, configs_path=None):
         raise NotImplementedError("This runtype is not implemented yet")
     per_call = _sample_batch()
     sampler = _sampler_name()
+    _weights_name()
     os.makedirs(args.save_path, exist_ok=True)
     rank, world, device, config, model, dm = _sampling_setup(args.model_name, configs_path, "1P")
     n_steps = int(os.environ.get("VDM4CDM_SAMPLING_STEPS", 250))
@@ -512,7 +540,7 @@ def train_uc_c(argv=None):
         raise SystemExit("usage: train_uc_c_from_field_name.py <field_name>")
     field_name = argv[0]
     log_dir, name = os.environ.get("VDM4CDM_LOG_DIR", "./data/logs/vdm4cdm-2D"), f"LH_uc_c_{field_name}"
-    resume, cfg_kw = _resume_path(log_dir, name), _cfg_dropout_kwargs()
+    resume, cfg_kw = _resume_path(log_dir, name), {**_cfg_dropout_kwargs(), **_ema_kwargs()}
     _seed_everything(42)
     cropsize = int(os.environ.get("VDM4CDM_CROPSIZE_2D", 256))
     batch_size = int(os.environ.get("VDM4CDM_BATCH_2D", 12))

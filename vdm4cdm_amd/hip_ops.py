@@ -1068,6 +1068,23 @@ def step_inc(step_ptr):
     check(_lib.lib().vdm_step_inc(_p(step_ptr), _s()), "vdm_step_inc")
 
 
+def ema_update(ema, p, decay, warmup=True, num_updates=None):
+    """vdm_ema_update: ema += (1 - d_k) * (p - ema) with d_k = min(decay, (1 + k) / (10 + k)) under warmup, k = num_updates[0] read on the
+    device (None: 0).  Contiguous fp32 tensors of equal size, any 4-byte alignment.  The counter is not bumped (step_inc)."""
+    _contig(ema, p, num_updates)
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.numel() == p.numel(), "ema_update: two fp32 tensors of one size"
+    assert num_updates is None or (num_updates.dtype == torch.int32 and num_updates.numel() >= 1)
+    check(_lib.lib().vdm_ema_update(_p(ema), _p(p), ema.numel(), float(decay), int(bool(warmup)), _p(num_updates), _s()), "vdm_ema_update")
+    return ema
+
+
+def swap_(a, b):
+    """vdm_swap: exchanges the contents of two contiguous fp32 tensors of equal size in place (no temporary)."""
+    _contig(a, b)
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.numel() == b.numel(), "swap_: two fp32 tensors of one size"
+    check(_lib.lib().vdm_swap(_p(a), _p(b), a.numel(), _s()), "vdm_swap")
+
+
 def sumsq(x, out, workspace=None):
     """out[0] += sum x^2.  workspace: the caller's 2048 floats instead of the cached scratch."""
     L = _lib.lib()

@@ -202,8 +202,12 @@ class LightSFM(nn.Module):
     """Stand-in for the reference's LightningModule ``sfm_model.LightSFM`` (same constructor / batch contract); the fit loop is
     vdm4cdm_amd.trainer.Trainer, as for LightVDM."""
 
-    def __init__(self, velocity_model, draw_figure=None, learning_rate=3.0e-4, **sfm_kwargs):
+    def __init__(self, velocity_model, draw_figure=None, learning_rate=3.0e-4, ema_decay=None, ema_warmup=True, **sfm_kwargs):
+        """ema_decay / ema_warmup: the exponential moving average of the weights, as for LightVDM."""
         super().__init__()
+        from .ema import check_ema_args
+        self.ema_decay, self.ema_warmup = check_ema_args(ema_decay, ema_warmup, "LightSFM(ema_decay)")      # (ValueError before any model work)
+        self.ema = None                       # the EmaWeights, built by configure_optimizers (the model then sits on its device)
         self.model = SFM(velocity_model, **sfm_kwargs)
         self.draw_figure = draw_figure
         self.learning_rate = learning_rate
@@ -252,13 +256,23 @@ class LightSFM(nn.Module):
         fused = all(p.is_cuda for p in self.parameters())
         opt = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, fused=fused, capturable=bool(capturable and fused))
         vm = self.model.velocity_model
-        if hasattr(vm, "mark_weights_dirty"):      # fused steps do not bump Tensor._version: tell the HIP executor to re-pack
+        from . import ema as _ema
+        ema = _ema.attach(self, vm, "model.velocity_model.")
+        if hasattr(vm, "mark_weights_dirty") or ema is not None:
             def _after_step(*_):
-                vm.mark_weights_dirty()
-                if hasattr(vm, "repack_weights"):
-                    vm.repack_weights()
+                if hasattr(vm, "mark_weights_dirty"):      # fused steps do not bump Tensor._version: tell the HIP executor to re-pack
+                    vm.mark_weights_dirty()
+                    if hasattr(vm, "repack_weights"):
+                        vm.repack_weights()
+                if ema is not None:                        # the optimizer hook: the eager, the DDP and the captured step all average
+                    ema.update()
             opt.register_step_post_hook(_after_step)
         return opt
+
+    def ema_weights(self):
+        """Context manager: inside, the model computes with the averaged weights (EmaWeights.swapped); without EMA a no-op."""
+        import contextlib
+        return self.ema.swapped() if self.ema is not None else contextlib.nullcontext()
 
     def draw_samples(self, x0=None, n_sampling_steps=100, batch_size=None, verbose=False, return_all=False, order=1, **kwargs):
         """Target-field samples for the source fields x0 (batch_size is implied by x0; accepted for the trainer's call).  order: 1

@@ -146,6 +146,14 @@ def cfg_dropout_record(model):
     return {"p_uncond": float(inner.p_uncond), "cfg_drop": str(inner.cfg_drop)}
 
 
+def ema_record(model):
+    """{"decay", "warmup"} of a module built with ema_decay= (None: it keeps no moving average of its weights) - what a resumed fit
+    must find in the checkpoint; read from the constructor's values, the EmaWeights itself exists only after configure_optimizers."""
+    if getattr(model, "ema_decay", None) is None:
+        return None
+    return {"decay": float(model.ema_decay), "warmup": bool(model.ema_warmup)}
+
+
 def read_checkpoint(path, mmap=False):
     """A checkpoint file on the host (tensors on the CPU; mmap: mapped, so that reading `global_step` does not read the weights)."""
     return torch.load(path, map_location="cpu", mmap=bool(mmap), weights_only=True)
@@ -192,6 +200,10 @@ class GraphedTrainStep:
         # none is created inside the capture.
         keep = [p.detach().clone() for p in params]
         keep_state = {id(v): (v, v.detach().clone()) for st in opt.state.values() for v in st.values() if torch.is_tensor(v)}
+        # the moving average of the weights (ema.EmaWeights, updated by the optimizer hook): its shadows and counter exist before the
+        # warm-up - nothing of it is allocated inside the capture - and are put back with the parameters
+        ema = getattr(model, "ema", None)
+        keep_ema = None if ema is None else ema.snapshot()
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             for _ in range(warmup):
@@ -206,6 +218,8 @@ class GraphedTrainStep:
                         elif torch.is_tensor(v):
                             v.zero_()
                 self.counter.zero_()
+                if ema is not None:
+                    ema.restore(keep_ema)
             sm = getattr(inner, "score_model", None)
             if hasattr(sm, "mark_weights_dirty"):
                 sm.mark_weights_dirty()
@@ -213,7 +227,7 @@ class GraphedTrainStep:
                     sm.repack_weights()
         cur.wait_stream(side)
         torch.cuda.synchronize(dev)
-        del keep, keep_state
+        del keep, keep_state, keep_ema
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.loss, self.gnorm = self._step()
@@ -310,6 +324,10 @@ class Trainer:
         payload = {"state_dict": model.state_dict(), "global_step": self.global_step, "epoch": epoch}
         if cfg_dropout_record(model) is not None:
             payload["cfg_dropout"] = cfg_dropout_record(model)
+        if getattr(model, "ema", None) is not None:          # the averaged weights under the model's own keys: a model loads them with
+            ema_state = model.ema.state_dict()               # load_state_dict(ck["ema_state_dict"]) (reads the device counter: one sync)
+            payload["ema_state_dict"] = ema_state.pop("shadow")
+            payload["ema"] = ema_state                       # {"decay", "warmup", "num_updates"}
         if state is not None:
             payload["trainer_state"] = state
         tmp = f"{path}.{os.getpid()}.tmp"
@@ -359,6 +377,15 @@ class Trainer:
                                      or (mine["p_uncond"] > 0 and saved["cfg_drop"] != mine["cfg_drop"])):
                 raise ValueError(f"{os.fspath(ckpt_path)} was written by a run with p_uncond={saved['p_uncond']} cfg_drop={saved['cfg_drop']!r}, "
                                  f"this model has p_uncond={mine['p_uncond']} cfg_drop={mine['cfg_drop']!r}: a resumed run must keep them")
+            saved, mine = resume[0].get("ema"), ema_record(model)      # so is the moving average of the weights
+            if (saved is None) != (mine is None) or (mine is not None and "ema_state_dict" not in resume[0]):
+                raise ValueError(f"{os.fspath(ckpt_path)} " + ("holds no EMA of the weights" if mine is not None else
+                                 f"holds an EMA of the weights (decay={saved['decay']})") + ", this model was built with ema_decay="
+                                 f"{None if mine is None else mine['decay']}: a run with EMA continues only from a checkpoint that holds it, "
+                                 "a run without EMA only from one that does not")
+            if mine is not None and (float(saved["decay"]) != mine["decay"] or bool(saved["warmup"]) != mine["warmup"]):
+                raise ValueError(f"{os.fspath(ckpt_path)} was written by a run with ema_decay={saved['decay']} ema_warmup={saved['warmup']}, "
+                                 f"this model has ema_decay={mine['decay']} ema_warmup={mine['warmup']}: a resumed run must keep them")
         dev = self.device
         if dev is None:
             dev = "cuda" if torch.cuda.is_available() else "cpu"
@@ -408,6 +435,8 @@ class Trainer:
             opt.load_state_dict(ts["optimizer"])
             for g, h in zip(opt.param_groups, how):          # (how the step is executed belongs to this run, not to the saved state)
                 g.update(h)
+            if getattr(model, "ema", None) is not None:      # (configure_optimizers built it from the loaded weights; now its own state)
+                model.ema.load_state_dict({**ck["ema"], "shadow": ck["ema_state_dict"]})
             set_rng_state(model, dev, rec["rng"])
             self.global_step, epoch, start_batch = int(ck["global_step"]), int(ck["epoch"]), int(ts["batches_into_epoch"])
             self._resumed_from = os.fspath(ckpt_path)
@@ -469,6 +498,14 @@ class Trainer:
 
     @torch.no_grad()
     def validate(self, model, datamodule):
+        """Validation loss, samples and figure - computed with the averaged weights when the model keeps an EMA (model.ema_weights():
+        parameters and shadows are exchanged in place and exchanged back, bit for bit, so the training that follows - a captured step
+        included - is unaffected)."""
+        import contextlib
+        with (model.ema_weights() if hasattr(model, "ema_weights") else contextlib.nullcontext()):
+            return self._validate(model, datamodule)
+
+    def _validate(self, model, datamodule):
         model.eval()
         losses, last = [], None
         world = getattr(self, "world", 1)

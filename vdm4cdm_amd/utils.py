@@ -109,6 +109,7 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
         raise ValueError(f"Unknown model type {config['type']}")
     from . import networks, vdm_model
     w_cfg, cfg_drop = guidance_knobs(config)             # (bad values: a ValueError before any model or GPU work)
+    weights = weights_knob(config)
     n_values = config.get("conditioning_values", 6)
     cropsize = config.get("cropsize", 128)
     score_model = networks.CUNet(
@@ -121,6 +122,11 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
         backend=backend, precision=precision or config.get("precision", "bf16"))
     path = config.get("ckpt_path")
     ck = torch.load(path, map_location="cpu") if (load_ckpt and path and os.path.exists(path)) else None
+    has_ema = isinstance(ck, dict) and ck.get("ema_state_dict") is not None
+    if weights == "ema" and load_ckpt and not has_ema:
+        raise ValueError(f"weights='ema' (VDM4CDM_WEIGHTS / config key weights): "
+                         + (f"the checkpoint {path} holds no ema_state_dict" if ck is not None else f"there is no checkpoint ({path!r})")
+                         + " - it was not trained with VDM4CDM_EMA_DECAY; use weights='raw'")
     recorded = ck.get("cfg_dropout") if isinstance(ck, dict) else None
     if w_cfg is not None:
         if cfg_drop is None:                               # by default what the checkpoint's training run dropped
@@ -132,11 +138,28 @@ def get_model(config, backend="hip", precision=None, load_ckpt=True):
                   + f": the network never saw the null token, its unguided branch (cfg_drop={cfg_drop!r}) is untrained", flush=True)
     vdm = vdm_model.LightVDM(score_model=score_model, draw_figure=None, gamma_max=13.3, learning_rate=3.0e-4,
                              **({} if w_cfg is None else {"w_cfg": w_cfg, "cfg_drop": cfg_drop}))
-    if ck is not None:
+    if ck is not None and has_ema and weights != "raw":
+        if weights is None:
+            print(f"[vdm4cdm_amd] {path} holds EMA weights (decay {ck.get('ema', {}).get('decay')}): sampling from them "
+                  "(VDM4CDM_WEIGHTS=raw for the last-step weights)", flush=True)
+        vdm.load_state_dict(ck["ema_state_dict"])
+    elif ck is not None:
         vdm.load_state_dict(ck["state_dict"])
     elif load_ckpt and path:
         print(f"[vdm4cdm_amd] checkpoint {path} not found: using seeded random weights (no trained weights ship with this repo)")
     return vdm
+
+
+def weights_knob(config):
+    """Which weights of a checkpoint a generation run samples from: $VDM4CDM_WEIGHTS / config["weights"] (the environment wins) -
+    "ema" (the checkpoint's ema_state_dict; a checkpoint without one is refused), "raw" (its state_dict), or None when neither is set:
+    the averaged weights if the checkpoint holds them, announced in one line, else the raw ones.  Any other value is a ValueError."""
+    import os
+    w = os.environ.get("VDM4CDM_WEIGHTS")
+    w = config.get("weights") if w in (None, "") else w
+    if w is not None and w not in ("ema", "raw"):
+        raise ValueError(f"weights={w!r} (VDM4CDM_WEIGHTS / config key weights): one of 'ema', 'raw'")
+    return w
 
 
 def guidance_knobs(config):

@@ -730,8 +730,13 @@ class LightVDM(nn.Module):
     reference scripts touch; the fit loop lives in vdm4cdm_amd.trainer.Trainer."""
 
     def __init__(self, score_model, draw_figure=None, gamma_min=-13.3, gamma_max=13.3, noise_schedule="fixed_linear",
-                 learning_rate=3.0e-4, **vdm_kwargs):
+                 learning_rate=3.0e-4, ema_decay=None, ema_warmup=True, **vdm_kwargs):
+        """ema_decay: keep an exponential moving average of the weights with this decay (ema.EmaWeights; e.g. 0.9999), updated after
+        every optimizer step; None or 0: none.  ema_warmup: d_k = min(ema_decay, (1 + k) / (10 + k)) at update k."""
         super().__init__()
+        from .ema import check_ema_args
+        self.ema_decay, self.ema_warmup = check_ema_args(ema_decay, ema_warmup, "LightVDM(ema_decay)")      # (ValueError before any model work)
+        self.ema = None                       # the EmaWeights, built by configure_optimizers (the model then sits on its device)
         self.model = VDM(score_model, noise_schedule=noise_schedule, gamma_min=gamma_min, gamma_max=gamma_max, **vdm_kwargs)
         self.draw_figure = draw_figure
         self.learning_rate = learning_rate
@@ -787,13 +792,25 @@ class LightVDM(nn.Module):
         fused = all(p.is_cuda for p in self.parameters())                       # one fused kernel over the flat vector
         opt = torch.optim.AdamW(self.parameters(), lr=self.learning_rate, fused=fused, capturable=bool(capturable and fused))       # D11
         sm = self.model.score_model
-        if hasattr(sm, "mark_weights_dirty"):      # fused steps do not bump Tensor._version: tell the HIP executor to re-pack
+        from . import ema as _ema
+        learned = self.model.noise_schedule == "learned_linear"
+        ema = _ema.attach(self, sm, "model.score_model.",
+                          {"model.gamma_b": self.model.gamma_b, "model.gamma_w": self.model.gamma_w} if learned else None)
+        if hasattr(sm, "mark_weights_dirty") or ema is not None:
             def _after_step(*_):
-                sm.mark_weights_dirty()
-                if hasattr(sm, "repack_weights"):
-                    sm.repack_weights()
+                if hasattr(sm, "mark_weights_dirty"):      # fused steps do not bump Tensor._version: tell the HIP executor to re-pack
+                    sm.mark_weights_dirty()
+                    if hasattr(sm, "repack_weights"):
+                        sm.repack_weights()
+                if ema is not None:                        # the optimizer hook: the eager, the DDP and the captured step all average
+                    ema.update()
             opt.register_step_post_hook(_after_step)
         return opt
+
+    def ema_weights(self):
+        """Context manager: inside, the model computes with the averaged weights (EmaWeights.swapped); without EMA a no-op."""
+        import contextlib
+        return self.ema.swapped() if self.ema is not None else contextlib.nullcontext()
 
     def rng_state_dict(self):
         """The random stream this module owns besides the shared training generators: the torch backend's per-rank noise generator
